@@ -6,8 +6,13 @@ One step = tube mask + forward (bf16 autocast) + fused masked-recon loss +
 backward + data-parallel gradient all-reduce (N > 1) + AdamW, exactly the body of
 train_one_epoch (train_ssl_mae.py:66-91) with inputs already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds
+what the headline figure does not need: the box calibration, the event-timed roofline probes,
+the CPU baselines and (fine-tune workload) the evaluation forward.  --dump-outputs DIR writes
+what the last timed step returned as DIR/<name>.npy.
 
 Rank 0 prints one JSON line (see the driver contract in DESIGN.md).
 """
@@ -43,12 +48,19 @@ def parse():
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--size", type=int, default=224)
     ap.add_argument("--mask-ratio", type=float, default=0.75)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: box calibration, roofline probes "
+                         "(HIP events around the probed kernels), CPU baselines, the fine-tune evaluation forward")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (loss, pred, mask index) "
+                         "as DIR/<name>.npy (float32 / float64; a fixed seeded sample of a large array)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline sweep")
     ap.add_argument("--attn-bwd-shape", default="",
                     help="A/B only: MFMA shape of the bf16 attention backward as 'D64,D32' (16 or 32 each; "
                          "default: the library's); reported in config when given")
     ap.add_argument("--no-calibration", action="store_true",
-                    help="skip the box calibration (bare MFMA loops + a 4.9 GB copy) before the timed steps")
+                    help="with --full: skip the box calibration (bare MFMA loops + a 4.9 GB copy) before the "
+                         "timed steps")
     ap.add_argument("--resident", default="",
                     help="encoder stages kept resident in HBM (no checkpoint recompute): "
                          "comma list, or 'none'; default: the model's auto policy")
@@ -60,8 +72,8 @@ def parse():
                          "auto = on for the MAE step (its stage-0 resident policy needs the arena's "
                          "coalescing heap), off for the fine-tune step")
     ap.add_argument("--probe", default="dec_attn_bwd",
-                    help="kernel group timed with events for the roofline line: dec_attn_bwd (the top-time "
-                         "kernels of the step: decoder attention dK/dV + dQ) or dec_attn_fwd")
+                    help="with --full: kernel group timed with events for the roofline line: dec_attn_bwd (the "
+                         "top-time kernels of the step: decoder attention dK/dV + dQ) or dec_attn_fwd")
     ap.add_argument("--model", default="tiny", choices=["tiny", "small"],
                     help="tiny: tiny_vit_21m_variant + 4-layer decoder (BASELINE C2); small: the build-defined "
                          "ViT-Small of BASELINE C3 (depths 2,2,12,2 + 8-layer decoder, SURVEY.md H8)")
@@ -254,6 +266,34 @@ class Probe:
         return sum(s.elapsed_time(e) for s, e in self.pairs) / len(self.pairs)
 
 
+DUMP_MAX_ELEMS = 2 * 2 ** 20     # per array: 8 MiB as float32 + 16 MiB of positions; a dump stays below 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each tensor as out_dir/<name>.npy, float32 (float64 stays float64;
+    integers up to 2^24 are exact in float32).  An array of more than DUMP_MAX_ELEMS elements is
+    written as a sample: the elements at DUMP_MAX_ELEMS flat positions drawn once from seed 0
+    (sorted, the same for every run of the same shape), the positions as <name>_positions.npy
+    in float64.  Returns {name: {"shape", "written"}} for the result line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        flat = t.reshape(-1)
+        n = flat.numel()
+        if n > DUMP_MAX_ELEMS:
+            pos = np.sort(np.random.default_rng(0).integers(0, n, size=DUMP_MAX_ELEMS, dtype=np.int64))
+            flat = flat[torch.from_numpy(pos).to(flat.device)]
+            np.save(os.path.join(out_dir, f"{name}_positions.npy"), pos.astype(np.float64))
+        else:
+            flat = flat.reshape(t.shape)
+        a = flat.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        info[name] = {"shape": list(t.shape), "written": int(a.size)}
+    return info
+
+
 def resident_used(model, frames, S):
     from ssl_mae_amd.tiny_vit import auto_resident_stages
     enc = model.encoder
@@ -324,9 +364,12 @@ def main():
     probe = Probe(args.probe)
     stem_probe = Probe("patch_embed_fwd")
     from ssl_mae_amd import tiny_vit as TV
-    stem_probe.wrap(TV.PatchEmbed, "run", lambda *a, **k: True)
+    if args.full:
+        stem_probe.wrap(TV.PatchEmbed, "run", lambda *a, **k: True)
     Ld = T * (S // 8) ** 2
-    if args.probe == "dec_attn_fwd":
+    if not args.full:                 # a plain run times the steps alone: no events around kernels
+        flop_per_launch = exec_flop_per_launch = None
+    elif args.probe == "dec_attn_fwd":
         probe.wrap(K, "attn_fwd", lambda qkv, N, L, H, D, *a, **k: D == 64 and L == Ld)
         flop_per_launch = 4.0 * B * 6 * Ld * Ld * 64        # S = QK^T and O = PV
         exec_flop_per_launch = flop_per_launch
@@ -345,8 +388,12 @@ def main():
     # backward on a side stream (N > 1)
     smdist.setup_data_parallel(model, opt, world)
 
-    def step(i):
-        loss, _, _ = train_step(model, clips[i % 2], opt, scaler, ssl_cfg, bf16=True)
+    last_out = []    # (pred, mask index) of the last timed step, kept only for --dump-outputs
+
+    def step(i, keep=False):
+        loss, pred, idx = train_step(model, clips[i % 2], opt, scaler, ssl_cfg, bf16=True)
+        if keep:
+            last_out[:] = [pred, idx]
         return loss
 
     if args.attn_bwd_shape:
@@ -356,12 +403,15 @@ def main():
         enc = model.encoder
         TV.check_memory_policy(B * T, S, True, dev, resident_used(model, B * T, S), lite_used(model, B * T, S),
                                key=(tuple(enc.depths), enc._sm_dec_depth))
+    torch.cuda.synchronize()
+    if rank == 0:
+        print("[bench] set-up done", file=sys.stderr, flush=True)
     for i in range(args.warmup):
         step(i)
     torch.cuda.synchronize()
     print(f"[bench] {args.warmup} warm-up steps done", file=sys.stderr, flush=True)
     calib = None
-    if not args.no_calibration:
+    if args.full and not args.no_calibration:
         try:
             calib = calibration(dev)
         except Exception as e:   # the calibration must not cost the bench line
@@ -370,14 +420,15 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    probe.active = True
-    stem_probe.active = True
+    probe.active = args.full
+    stem_probe.active = args.full
+    dump = bool(args.dump_outputs) and rank == 0
     t0 = time.perf_counter()
     loss_vals, step_end = [], []
     for i in range(args.steps):
         # the reference syncs on the loss every step (total_loss += loss.item(),
         # train_ssl_mae.py:91): so does the timed loop
-        loss_vals.append(float(step(i).item()))
+        loss_vals.append(float(step(i, keep=dump and i == args.steps - 1).item()))
         step_end.append(time.perf_counter())
         if rank == 0 and (i + 1) % 10 == 0:
             print(f"[bench] {i + 1}/{args.steps} timed steps", file=sys.stderr, flush=True)
@@ -440,7 +491,7 @@ def main():
                                    "avg_launch_ms": round(savg, 3), "launches": len(stem_probe.pairs)}
         step_tflops = value / world * TRAIN_TFLOP_PER_CLIP if not small else None
         cpu = None
-        if not args.no_cpu_baseline and world == 1 and not small:
+        if args.full and not args.no_cpu_baseline and world == 1 and not small:
             try:
                 cpu = cpu_baseline(T, S, r)
             except Exception as e:  # the baseline must not kill the bench line
@@ -475,8 +526,14 @@ def main():
             "loss_first_last": [round(loss_vals[0], 5), round(loss_vals[-1], 5)],
             "loss_item_per_step": True,
             "cpu_baseline": cpu,
-            "cpu_baseline_reference": reference_cpu() if not small else None,
+            "cpu_baseline_reference": reference_cpu() if args.full and not small else None,
+            "full": args.full,
         }
+        if dump:
+            line["outputs"] = dump_outputs(args.dump_outputs, {
+                "loss": torch.tensor(loss_vals[-1], dtype=torch.float64),
+                "loss_per_step": torch.tensor(loss_vals, dtype=torch.float64),
+                "pred": last_out[0], "mask_index": last_out[1]})
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()
@@ -537,7 +594,7 @@ def bench_finetune(args, rank, world, dev):
         model.eval()
         with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
             return model(clip)
-    el_eval, _ = timed(eval_step, args.steps, 1)
+    el_eval = timed(eval_step, args.steps, 1)[0] if args.full else None
     if rank == 0:
         value = B * world * args.steps / el
         line = {"metric": "clips/sec (16x3x112x112) frozen-encoder fine-tune step (linear probe)",
@@ -550,9 +607,12 @@ def bench_finetune(args, rank, world, dev):
                                        "the head, T=16, 112x112, bf16 autocast",
                            "global_batch": B * world, "per_gpu_batch": B, "frames": T, "image_size": S,
                            "parallelism": f"dp{world}"},
-                "eval_clips_per_s": round(B * world * args.steps / el_eval, 2),
+                "eval_clips_per_s": round(B * world * args.steps / el_eval, 2) if el_eval else None,
                 "loss_last": round(float(loss.item()), 5),
-                "peak_mem_gib": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1)}
+                "peak_mem_gib": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1),
+                "full": args.full}
+        if args.dump_outputs:
+            line["outputs"] = dump_outputs(args.dump_outputs, {"loss": loss.double()})
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()
