@@ -129,6 +129,31 @@ int64_t sm_linear_dw_se_workspace_bytes(int rows, int nout, int nin);
 int sm_linear_dw_se(int rows, int nout, int nin, const void* dy, const void* a2, const float* act_mean,
                     const float* act_rstd, const float* act_w, const float* act_b, int act_gelu, const float* gate,
                     int hw, float* dW, int accumulate, void* ws, int64_t ws_bytes, hipStream_t stream);
+/* Data gradient over an A operand made of two buffers: dx[M][N] = [a1 | a2] w (+ bias[n])
+ * (+ residual[M][N]); a1 [M][K1] (row stride lda1), a2 [M][K2] (row stride lda2), w [K1 + K2][N],
+ * dx / residual [M][N], all bf16; bias fp32, nullable like residual.  Bit-identical to the plain
+ * data gradient of a materialised concatenation.  K1 % 64 == 0, K2 % 8 == 0, N % 8 == 0
+ * (else -2). */
+int sm_linear_dx2(int M, int N, int K1, int K2, const void* a1, int64_t lda1, const void* a2, int64_t lda2,
+                  const void* w, const float* bias, const void* residual, void* dx, hipStream_t stream);
+/* BN0's backward dx map folded into the MBConv expand conv's gradient GEMMs (tiny_vit.py:43-48).
+ * With a1 = x W^T, xhat = (a1 - mean) rstd, dz and coef = (k0, k1) [2][mid] from
+ * sm_dwconv_bn_bwd_dz:  da1 = omega dz - delta a1 + c  per channel, omega = bn_w rstd,
+ * delta = omega rstd k1, c = omega (rstd k1 mean - k0).  Then
+ *   dX  = dz W' - x T + r0,  W' = diag(omega) W, T = W^T diag(delta) W, r0 = c^T W
+ *   dW += diag(omega) P - diag(delta) (W G) + c s^T,  P = dz^T x, G = x^T x, s = column sums of x.
+ * _prep: w [mid][Cin] bf16 -> wst [mid + Cin][Cin] bf16 = [W'; -T] (T summed in fp32), r0 [Cin],
+ * vec [3][mid] = omega, delta, c.  _dw: P [mid][Cin], G [Cin][Cin], s [Cin] fp32 over the M rows,
+ * combined in fp64 into dW [mid][Cin] (+=).  x_mean .. x_b (all or none): the block input is
+ * x = BN(xs) of a stored xs (no GELU); the data-gradient GEMM, G and s then read xs (P the
+ * BatchNorm output) and the affine goes into -T, r0 and the combination.
+ * mid <= 2048, Cin <= 1024. */
+int sm_mbconv_fold_prep(int mid, int Cin, const float* coef, const float* bn_mean, const float* bn_rstd,
+                        const float* bn_w, const void* w, const float* x_mean, const float* x_rstd,
+                        const float* x_w, const float* x_b, void* wst, float* r0, float* vec, hipStream_t st);
+int sm_mbconv_fold_dw(int mid, int Cin, int64_t M, const float* vec, const void* w, const float* P, const float* G,
+                      const float* s, const float* x_mean, const float* x_rstd, const float* x_w, const float* x_b,
+                      float* dW, hipStream_t st);
 
 /* ---- fused attention (tiny_vit.py:103 F.scaled_dot_product_attention;
  * torch MultiheadAttention core of the decoder, mae_vit_adapter.py:40-48).
@@ -297,6 +322,13 @@ int sm_dwconv_bn_bwd(int F, int H, int W, int C, const void* dy, const void* x, 
 int sm_dwconv_s2_bn_bwd(int F, int H, int W, int C, const void* dy, const void* x, const float* bn_mean,
                         const float* bn_rstd, const float* bn_w, const float* bn_b, int bn_gelu, const float* w,
                         void* dx, float* dw, float* dgamma, float* dbeta, void* ws, int64_t ws_bytes,
+                        hipStream_t st);
+/* The first pass alone (stride 1 or 2; same shapes, outputs and workspace): dz = g GELU'(BN(x))
+ * stays in dz [F][H][W][C], coef [2][C] = mean(dz), mean(dz xhat); the BatchNorm's dx map
+ * dx = bn_w rstd (dz - coef[0] - xhat coef[1]) is left to the consumer (sm_mbconv_fold_prep). */
+int sm_dwconv_bn_bwd_dz(int stride, int F, int H, int W, int C, const void* dy, const void* x, const float* bn_mean,
+                        const float* bn_rstd, const float* bn_w, const float* bn_b, int bn_gelu, const float* w,
+                        void* dz, float* dw, float* dgamma, float* dbeta, float* coef, void* ws, int64_t ws_bytes,
                         hipStream_t st);
 int sm_dwconv_bwd(int dtype, const void* dy, const void* x, const float* w, void* dx, float* dw, int F,
                   int H, int W, int C, int stride, void* ws, int64_t ws_bytes, hipStream_t st);

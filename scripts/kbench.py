@@ -331,6 +331,8 @@ def mbconv(args):
     g0, b0 = torch.zeros(C, device=dev), torch.zeros(C, device=dev)
     rep("dwconv_bn_bwd s1 (2 passes)", timeit(lambda: K.dwconv_bn_bwd(y, a, act, w, dw, g0, b0, Fn, H, W, C),
                                               args.iters), 5)
+    rep("dwconv_bn_bwd_dz s1 (folded)", timeit(lambda: K.dwconv_bn_bwd_dz(y, a, act, w, dw, g0, b0, Fn, H, W, C),
+                                               args.iters), 3)
     rep("dwconv_fused s2", timeit(lambda: K.dwconv_fused(a, act, w, Fn, H, W, C, 2), args.iters), 1.25)
     y2 = K.dwconv_fused(a, act, w, Fn, H, W, C, 2)
     rep("s2 bwd unfused (dw bwd+bn_bwd)", timeit(lambda: K.bn_bwd(K.dwconv_fused_bwd(y2, a, act, w, dw, Fn, H, W, C, 2),
@@ -339,6 +341,9 @@ def mbconv(args):
     rep("dwconv_bn_bwd s2 (2 passes)", timeit(lambda: K.dwconv_bn_bwd(y2, a, act, w, dw, torch.zeros(C, device=dev),
                                                                        torch.zeros(C, device=dev), Fn, H, W, C,
                                                                        stride=2), args.iters), 4.25)
+    rep("dwconv_bn_bwd_dz s2 (folded)", timeit(lambda: K.dwconv_bn_bwd_dz(y2, a, act, w, dw, torch.zeros(C, device=dev),
+                                                                          torch.zeros(C, device=dev), Fn, H, W, C,
+                                                                          stride=2), args.iters), 2.25)
     del y2
     w1 = torch.randn(C // 4, C, device=dev) * 0.1
     w2 = torch.randn(C, C // 4, device=dev) * 0.1
@@ -352,10 +357,50 @@ def mbconv(args):
                                     args.iters), 5)
 
 
+def bn0fold(args):
+    """The expand conv's gradients of a stage-0 MBConv (96 -> 384 at 112^2) behind the depthwise
+    backward's first pass: da1 stored + plain GEMMs against BN0's dx map folded into the GEMMs
+    (csrc/mbfold.hip).  --only dx2 / old / fold: one group (counter passes)."""
+    Fn, H, W, C, Cin = args.batch * 8, 112, 112, 384, 96
+    M = Fn * H * W
+    dev = "cuda"
+    x = (torch.randn(M, Cin, device=dev) + 0.3).to(torch.bfloat16)
+    wexp = (torch.randn(C, Cin, device=dev) * 0.15).to(torch.bfloat16)
+    a1 = K.linear(x, wexp)
+    m, r = K.bn_stats(a1)
+    gam = torch.rand(C, device=dev) + 0.5
+    dz = (torch.randn(M, C, device=dev) * 1e-2).to(torch.bfloat16)
+    coef = torch.stack([dz[:4096].float().mean(0), (dz[:4096].float() * (a1[:4096].float() - m) * r).mean(0)])
+    res = (torch.randn(M, Cin, device=dev) * 1e-2).to(torch.bfloat16)
+    sink = torch.zeros(C, Cin, device=dev)
+    T, t = M * C * 2 / 1e9, M * Cin * 2 / 1e9
+
+    def rep(name, ms, gb):
+        print(f"{name:36s} {ms:8.2f} ms  {gb / ms:6.2f} TB/s ({gb:.1f} GB)", flush=True)
+    wst, r0, vec = K.mbconv_fold_prep(coef, m, r, gam, wexp)
+    if args.only in ("", "fold", "dx2"):
+        rep("linear_dx2 [dz | x] (+r0, +res)", timeit(lambda: K.linear_dx2(dz, x, wst, bias=r0, residual=res),
+                                                      args.iters), T + 3 * t)
+    if args.only in ("", "fold"):
+        P = torch.empty(C, Cin, device=dev)
+        gram, xsum = torch.zeros(Cin, Cin, device=dev), torch.zeros(Cin, device=dev)
+        rep("fold prep", timeit(lambda: K.mbconv_fold_prep(coef, m, r, gam, wexp), args.iters), 0.0)
+        rep("P = dz^T x", timeit(lambda: K.linear_dw(dz, x, P, accumulate=False), args.iters), T + t)
+        rep("G = x^T x, s", timeit(lambda: K.linear_dw_bias(x, x, gram, xsum), args.iters), 2 * t)
+        rep("fold combine", timeit(lambda: K.mbconv_fold_dw(vec, wexp, P, gram, xsum, M, sink), args.iters), 0.0)
+        # the same data gradient as two launches of the plain kernels (x (-T) + r0 + res, then dz W')
+        wp, nt_t = wst[:C].contiguous(), wst[C:].t().contiguous()
+        rep("two launches: linear + linear_dx", timeit(
+            lambda: K.linear_dx(dz, wp, residual=K.linear(x, nt_t, r0, residual=res)), args.iters), T + 5 * t)
+    if args.only in ("", "old"):
+        rep("linear_dx da1 (+res)", timeit(lambda: K.linear_dx(dz, wexp, residual=res), args.iters), T + 2 * t)
+        rep("linear_dw da1", timeit(lambda: K.linear_dw(dz, x, sink), args.iters), T + t)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["attn", "gemm", "gemmk", "mbconv", "dw", "dwx", "dwse", "stem", "gemmw",
-                                     "bnstats", "dxgelu"])
+                                     "bnstats", "dxgelu", "bn0fold"])
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--drop", type=float, default=0.1)
     ap.add_argument("--iters", type=int, default=5)
@@ -367,4 +412,4 @@ if __name__ == "__main__":
     from ssl_mae_amd.build import build
     build()
     {"attn": attn, "gemm": gemm, "gemmk": gemmk, "mbconv": mbconv, "dw": dw, "dwx": dwx, "dwse": dwse, "stem": stem, "gemmw": gemmw,
-     "bnstats": bnstats, "dxgelu": dxgelu}[a.what](a)
+     "bnstats": bnstats, "dxgelu": dxgelu, "bn0fold": bn0fold}[a.what](a)

@@ -2094,7 +2094,7 @@ extern "C" int64_t sm_dwconv_bn_bwd_workspace_bytes(int F, int H, int W, int C) 
 static int dwconv_bn_bwd(int stride, int F, int H, int W, int C, const void* dy, const void* x, const float* bn_mean,
                          const float* bn_rstd, const float* bn_w, const float* bn_b, int bn_gelu, const float* w,
                          void* dx, float* dw, float* dgamma, float* dbeta, void* ws, int64_t ws_bytes,
-                         hipStream_t st) {
+                         hipStream_t st, float* coef_out = nullptr) {
   if (bad_stride(stride)) return -2;
   const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
   size_t lds = stride == 1 ? dwf_lds_bytes(W, 1) + DWB_PAD + 4 * DWF_CB * 4
@@ -2108,6 +2108,8 @@ static int dwconv_bn_bwd(int stride, int F, int H, int W, int C, const void* dy,
   float* part_bn = part_w + (int64_t)F * C * 9;
   float* coef = part_bn + (int64_t)F * 2 * C;
   double* sums = (double*)(((uintptr_t)(coef + 2 * C) + 7) & ~(uintptr_t)7);
+  // coef_out: the caller keeps dz and the coefficients (sm_dwconv_bn_bwd_dz); no dx pass
+  if (coef_out) coef = coef_out;
   ChanAffine bn{bn_mean, bn_rstd, bn_w, bn_b, bn_gelu};
   const dim3 grid((C / DWF_CB) * F);
   if (stride == 2) {
@@ -2136,6 +2138,10 @@ static int dwconv_bn_bwd(int stride, int F, int H, int W, int C, const void* dy,
   const int64_t M = (int64_t)F * H * W;
   hipLaunchKernelGGL(se_bn_finalize_kernel, dim3((C + 127) / 128), dim3(128), 0, st, sums, M, C, dgamma, dbeta,
                      coef);
+  if (coef_out) {
+    SM_CHECK_LAUNCH();
+    return 0;
+  }
   int64_t rpb = (M + 4095) / 4096;
   if (rpb < 16) rpb = 16;
   hipLaunchKernelGGL(dwb_dx_kernel, dim3((unsigned)((M + rpb - 1) / rpb)), dim3(256), 0, st, (const __bf16*)x, bn,
@@ -2159,6 +2165,18 @@ extern "C" int sm_dwconv_s2_bn_bwd(int F, int H, int W, int C, const void* dy, c
                                    int64_t ws_bytes, hipStream_t st) {
   return dwconv_bn_bwd(2, F, H, W, C, dy, x, bn_mean, bn_rstd, bn_w, bn_b, bn_gelu, w, dx, dw, dgamma, dbeta, ws,
                        ws_bytes, st);
+}
+
+// The first pass alone (stride 1 or 2): dz = g GELU'(BN(x)) stays in `dz`, coef [2][C] =
+// mean(dz), mean(dz xhat); dw / dgamma / dbeta as above.  The BatchNorm's dx map
+// w rstd (dz - coef[0] - xhat coef[1]) is left to the consumer (sm_mbconv_fold_*).
+extern "C" int sm_dwconv_bn_bwd_dz(int stride, int F, int H, int W, int C, const void* dy, const void* x,
+                                   const float* bn_mean, const float* bn_rstd, const float* bn_w, const float* bn_b,
+                                   int bn_gelu, const float* w, void* dz, float* dw, float* dgamma, float* dbeta,
+                                   float* coef, void* ws, int64_t ws_bytes, hipStream_t st) {
+  if (!coef) return -2;
+  return dwconv_bn_bwd(stride, F, H, W, C, dy, x, bn_mean, bn_rstd, bn_w, bn_b, bn_gelu, w, dz, dw, dgamma, dbeta, ws,
+                       ws_bytes, st, coef);
 }
 
 extern "C" int64_t sm_dwconv_wgrad_workspace_bytes(int F, int H, int W, int C, int stride) {

@@ -64,6 +64,12 @@ struct GemmArgs {
   // IMP 9 only (sm_linear_dx_gelu): side output of the GELU input aux, aux_out = bf16(GELU(aux)
   // * dropout keep / (1 - p)) = sm_gelu_fwd(aux) -- the fc2 weight gradient's operand
   void* aux_out;
+  // IMP 14 only (sm_linear_dx2): a K-major A operand made of two K segments, columns [0, k1)
+  // from A (ld lda) and columns [k1, K) from A2 (ld lda2); k1 % BKT == 0, so a K-step lies in
+  // one segment
+  const void* A2;
+  int64_t lda2;
+  int k1;
 };
 
 template <typename TC>
@@ -991,8 +997,20 @@ __global__ __launch_bounds__(BMV * 2, (BMV == 256 && IMP != 5 && IMP != 6 && IMP
   // (W + 1)-pixel halo; B's advances with K (its rows are pixels)
   const int64_t cbase = -(int64_t)(g.cW + 1) * g.cC;
   auto load_a = [&](int k0, uint4 (&r)[TileLoader<BMV, NT, AK>::CH]) {
-    if constexpr (IMP == 1 || IMP == 10) cla.load(panel_rsrc(A, (int64_t)m0 * g.cC + cbase), g, ke, r);
-    else tla.load(panel_rsrc(A, abase + k0 * astep), ke - k0, r);
+    if constexpr (IMP == 1 || IMP == 10) {
+      cla.load(panel_rsrc(A, (int64_t)m0 * g.cC + cbase), g, ke, r);
+    } else if constexpr (IMP == 14) {
+      // two K segments: the loader's row offsets are rebuilt for the second segment's ld at
+      // its first K-step (block-uniform; the offsets of a step are dead once it is loaded)
+      if (k0 < g.k1) {
+        tla.load(panel_rsrc(A, abase + k0), g.k1 - k0, r);
+      } else {
+        if (k0 == g.k1) tla.init(g.lda2, g.M - m0);
+        tla.load(panel_rsrc((const __bf16*)g.A2, (int64_t)m0 * g.lda2 + (k0 - g.k1)), ke - k0, r);
+      }
+    } else {
+      tla.load(panel_rsrc(A, abase + k0 * astep), ke - k0, r);
+    }
   };
   auto load_b = [&](int k0, uint4 (&r)[TileLoader<BNV, NT, BK>::CH]) {
     if constexpr (IMP == 2) clb.load(panel_rsrc(B, (int64_t)k0 * g.cC + cbase), g, ke - k0, r);
@@ -2320,6 +2338,31 @@ extern "C" int sm_linear_dx_gelu(int M, int N, int K, const void* dy, const void
   }
   if (v == 2) hipLaunchKernelGGL((gemm_bf16_v2<true, false, __bf16, true, 256, 9>), dim3(tiles), dim3(512), 0, stream, g);
   else hipLaunchKernelGGL((gemm_bf16_v2<true, false, __bf16, true, 128, 9>), dim3(tiles), dim3(256), 0, stream, g);
+  SM_CHECK_LAUNCH();
+  return 0;
+}
+
+// Data gradient over an A operand made of two buffers (the MBConv expand conv with BN0's
+// backward folded into its weights, sm_mbconv_fold_prep): dx[M][N] = [a1 | a2] w (+ bias[n])
+// (+ residual), a1 [M][K1] (ld lda1), a2 [M][K2] (ld lda2), w [K1 + K2][N], all bf16 --
+// the same K loop as the plain data gradient on a materialised [a1 | a2] (bit-identical), without
+// the concatenation.  K1 % 64 == 0 (a K-step lies in one segment), K2 % 8 == 0, N % 8 == 0.
+extern "C" int sm_linear_dx2(int M, int N, int K1, int K2, const void* a1, int64_t lda1, const void* a2, int64_t lda2,
+                             const void* w, const float* bias, const void* residual, void* dx, hipStream_t stream) {
+  if (M <= 0 || N <= 0) return 0;
+  if (K1 <= 0 || K1 % BKT || K2 <= 0 || K2 % 8 || N % 8 || lda1 < K1 || lda2 < K2 || lda1 % 8 || lda2 % 8 ||
+      a1 == nullptr || a2 == nullptr || w == nullptr || dx == nullptr ||
+      (((uintptr_t)a1 | (uintptr_t)a2 | (uintptr_t)w | (uintptr_t)dx | (uintptr_t)residual) & 15))
+    return -2;
+  GemmArgs g{};
+  g.M = M; g.N = N; g.K = K1 + K2; g.A = a1; g.lda = lda1; g.B = w; g.ldb = N; g.C = dx; g.ldc = N;
+  g.A2 = a2; g.lda2 = lda2; g.k1 = K1;
+  g.bias = bias; g.alpha = 1.f; g.beta = residual ? 1.f : 0.f; g.R = residual;
+  g.rows_per_group = 1; g.k_begin = 0; g.k_chunk = g.K;
+  const int v = gemm_variant(M, N, g.K) == 2 ? 2 : 3;
+  const int tiles = ((N + 127) / 128) * ((M + variant_bm(v) - 1) / variant_bm(v));
+  if (v == 2) hipLaunchKernelGGL((gemm_bf16_v2<true, false, __bf16, true, 256, 14>), dim3(tiles), dim3(512), 0, stream, g);
+  else hipLaunchKernelGGL((gemm_bf16_v2<true, false, __bf16, true, 128, 14>), dim3(tiles), dim3(256), 0, stream, g);
   SM_CHECK_LAUNCH();
   return 0;
 }

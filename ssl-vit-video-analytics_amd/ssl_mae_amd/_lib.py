@@ -110,6 +110,10 @@ _SIGS = {
     "sm_dwconv_bn_bwd_workspace_bytes": (_c_i64, [_c_i32] * 4),
     "sm_dwconv_bn_bwd": (_c_i32, [_c_i32] * 4 + [_c_p] * 6 + [_c_i32] + [_c_p] * 6 + [_c_i64, _c_p]),
     "sm_dwconv_s2_bn_bwd": (_c_i32, [_c_i32] * 4 + [_c_p] * 6 + [_c_i32] + [_c_p] * 6 + [_c_i64, _c_p]),
+    "sm_dwconv_bn_bwd_dz": (_c_i32, [_c_i32] * 5 + [_c_p] * 6 + [_c_i32] + [_c_p] * 7 + [_c_i64, _c_p]),
+    "sm_linear_dx2": (_c_i32, [_c_i32] * 4 + [_c_p, _c_i64, _c_p, _c_i64] + [_c_p] * 5),
+    "sm_mbconv_fold_prep": (_c_i32, [_c_i32, _c_i32] + [_c_p] * 13),
+    "sm_mbconv_fold_dw": (_c_i32, [_c_i32, _c_i32, _c_i64] + [_c_p] * 11),
     "sm_bn_eval_params": (_c_i32, [_c_p, _c_p, _c_i32, _c_f32, _c_p, _c_p, _c_p]),
     "sm_segment_mean": (_c_i32, [_c_i32, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p]),
     "sm_segment_mean_bwd": (_c_i32, [_c_i32, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p]),

@@ -22,6 +22,10 @@ import torch
 
 from . import ops as K    # every kernel launch through the torch.ops.ssl_mae dispatcher
 
+# MBConvFn.backward: fold BN0's dx map into the expand conv's gradient GEMMs where the widths
+# allow it (False: the two-pass dwconv_bn_bwd + plain GEMMs everywhere; tests and A/B runs)
+BN0_FOLD = True
+
 
 class Mode:
     """Per-forward execution mode: precision and the base of the counter-hash RNG
@@ -335,6 +339,28 @@ class MBConvFn(torch.autograd.Function):
         K.gemm(dz1, pooled, G(w_fc0), R, mid, Fr, 1, 1, R, mid, mid, beta=1.0)
         if a1 is None:
             a1 = expand(x)
+        x2d = x.reshape(-1, Cin)
+        if ctx.fused and BN0_FOLD and mid % 64 == 0 and Cin % 8 == 0 and Cin <= mid // 2:
+            # BN0's dx map folded into the expand conv's gradient GEMMs: the depthwise backward
+            # keeps dz (no streaming pass over (dz, a1)), da1 = omega dz - delta a1 + c is never
+            # stored; a1 = x W^T puts the a1 term into Cin-wide factors (csrc/mbfold.hip)
+            act0 = (m0, r0, g0.detach(), b0.detach(), True)
+            dz, coef = K.dwconv_bn_bwd_dz(da2, a1, act0, w_dw.detach().view(mid, 9), G(w_dw).view(mid, 9), G(g0),
+                                          G(b0), Fr, H, Wd, mid, stride=s)
+            del da2, a1
+            wb = W(w_exp, mode).view(mid, Cin)
+            wst, r0f, vec = K.mbconv_fold_prep(coef, m0, r0, g0.detach(), wb)
+            # a BatchNorm-folded input is formed once here (the narrow tensor: Cin = mid / 4), so the
+            # block computes bit for bit what it does from a stored BatchNorm output
+            xf = x2d if xbn is None else K.bn_apply(x2d, *xbn[:4], gelu=False)
+            P = K.linear_dw(dz, xf, torch.empty((mid, Cin), dtype=torch.float32, device=dz.device), accumulate=False)
+            gram = torch.zeros((Cin, Cin), dtype=torch.float32, device=dz.device)
+            xsum = torch.zeros(Cin, dtype=torch.float32, device=dz.device)
+            K.linear_dw_bias(xf, xf, gram, xsum)       # G = x^T x, s = column sums
+            K.mbconv_fold_dw(vec, wb, P, gram, xsum, xf.shape[0], G(w_exp).view(mid, Cin))
+            dx = K.linear_dx2(dz, xf, wst, bias=r0f, residual=dout2d if st.res else None)
+            _done(*ctx.params)
+            return (dx.view(Fr, H, Wd, Cin),) + (None,) * 12
         if ctx.fused:
             # depthwise + BN0/GELU backward in two passes over (da2, a1); dh1 never stored
             act0 = (m0, r0, g0.detach(), b0.detach(), True)
@@ -349,7 +375,6 @@ class MBConvFn(torch.autograd.Function):
         if dh1 is not None:
             da1 = K.bn_bwd(dh1, a1, m0, r0, g0.detach(), b0.detach(), True, G(g0), G(b0))
             del dh1
-        x2d = x.reshape(-1, Cin)
         if xbn is not None:     # B operand bf16(BN(x)) formed on load (no gate)
             K.linear_dw_se(da1, x2d, xbn, None, 0, G(w_exp).view(mid, Cin))
         else:

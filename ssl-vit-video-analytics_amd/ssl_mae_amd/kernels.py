@@ -694,6 +694,76 @@ def dwconv_bn_bwd(dy, x, act, w, dw_sink, dg_sink, db_sink, F, H, W, C, stride=1
     return dx
 
 
+def dwconv_bn_bwd_dz(dy, x, act, w, dw_sink, dg_sink, db_sink, F, H, W, C, stride=1):
+    """dwconv_bn_bwd without its streaming dx pass (sm_dwconv_bn_bwd_dz): returns (dz, coef) with
+    dz = g GELU'(BN(x)) [F*H*W, C] bf16 and coef [2, C] = mean(dz), mean(dz xhat); the sinks
+    as dwconv_bn_bwd.  The BatchNorm's dx map is folded into the consumers (mbconv_fold_*)."""
+    _chk(dy, x)
+    dz = torch.empty_like(x)
+    coef = torch.empty((2, C), dtype=torch.float32, device=x.device)
+    nbytes = query("sm_dwconv_bn_bwd_workspace_bytes", F, H, W, C)
+    ws = _ws(nbytes, x.device)
+    a = _act_args(act)
+    call("sm_dwconv_bn_bwd_dz", int(stride), F, H, W, C, ptr(dy), ptr(x), a[0], a[1], a[2], a[3], a[4], ptr(w),
+         ptr(dz), ptr(dw_sink), ptr(dg_sink), ptr(db_sink), ptr(coef), ptr(ws), nbytes, stream())
+    return dz, coef
+
+
+def _xbn_args(xbn):
+    return [None] * 4 if xbn is None else [ptr(t) for t in xbn[:4]]
+
+
+def mbconv_fold_prep(coef, mean, rstd, gamma, w, xbn=None):
+    """BN0's backward folded into the expand conv's gradient weights (sm_mbconv_fold_prep):
+    returns (wst [mid + Cin, Cin] bf16 = [diag(omega) w; -w^T diag(delta) w], r0 [Cin] = c^T w,
+    vec [3, mid] = omega, delta, c) from coef [2, mid], BN0's (mean, rstd, gamma) and the bf16
+    expand weight w [mid, Cin].  xbn = (mean, rstd, weight, bias): the block input is the
+    BatchNorm of a stored tensor; its affine goes into -T and r0 (the GEMM reads the stored one)."""
+    _chk(coef, mean, rstd, gamma, w)
+    mid, Cin = w.shape
+    if w.dtype != torch.bfloat16 or not w.is_contiguous() or tuple(coef.shape) != (2, mid):
+        raise _lib.KernelError("mbconv_fold_prep: contiguous bf16 w [mid, Cin], coef [2, mid]")
+    wst = torch.empty((mid + Cin, Cin), dtype=torch.bfloat16, device=w.device)
+    r0 = torch.empty(Cin, dtype=torch.float32, device=w.device)
+    vec = torch.empty((3, mid), dtype=torch.float32, device=w.device)
+    call("sm_mbconv_fold_prep", mid, Cin, ptr(coef), ptr(mean), ptr(rstd), ptr(gamma), ptr(w), *_xbn_args(xbn),
+         ptr(wst), ptr(r0), ptr(vec), stream())
+    return wst, r0, vec
+
+
+def mbconv_fold_dw(vec, w, P, G, s, M, grad_sink, xbn=None):
+    """grad_sink [mid, Cin] += diag(omega) P - diag(delta) (w G) + c s^T (sm_mbconv_fold_dw; fp64):
+    the expand weight gradient from P = dz^T x, G = x^T x, s = column sums of x over M rows
+    (xbn: G and s are the stored input's, P the BatchNorm output's)."""
+    _chk(vec, w, P, G, s, grad_sink)
+    mid, Cin = w.shape
+    if (tuple(P.shape) != (mid, Cin) or tuple(G.shape) != (Cin, Cin) or s.numel() != Cin
+            or tuple(grad_sink.shape) != (mid, Cin) or tuple(vec.shape) != (3, mid) or w.dtype != torch.bfloat16):
+        raise _lib.KernelError("mbconv_fold_dw: shape mismatch")
+    call("sm_mbconv_fold_dw", mid, Cin, int(M), ptr(vec), ptr(w), ptr(P), ptr(G), ptr(s), *_xbn_args(xbn),
+         ptr(grad_sink), stream())
+    return grad_sink
+
+
+def linear_dx2(a1, a2, w, bias=None, residual=None):
+    """dx [M, N] = [a1 | a2] @ w (+ bias) (+ residual) without the concatenation (sm_linear_dx2):
+    a1 [M, K1], a2 [M, K2] bf16 with unit column stride (row strides free), w [K1 + K2, N];
+    K1 % 64 == 0."""
+    _chk(a1, a2, w, bias, residual)
+    M, K1 = a1.shape
+    K2 = a2.shape[1]
+    N = w.shape[1]
+    if (a2.shape[0] != M or w.shape[0] != K1 + K2 or a1.stride(1) != 1 or a2.stride(1) != 1 or not w.is_contiguous()
+            or any(t.dtype != torch.bfloat16 for t in (a1, a2, w))
+            or (residual is not None and (tuple(residual.shape) != (M, N) or residual.dtype != torch.bfloat16
+                                          or not residual.is_contiguous()))):
+        raise _lib.KernelError("linear_dx2: bf16 a1 [M,K1], a2 [M,K2], w [K1+K2,N], residual [M,N]")
+    dx = torch.empty((M, N), dtype=torch.bfloat16, device=a1.device)
+    call("sm_linear_dx2", M, N, K1, K2, ptr(a1), a1.stride(0), ptr(a2), a2.stride(0), ptr(w), ptr(bias),
+         ptr(residual), ptr(dx), stream())
+    return dx
+
+
 def se_fwd(x, F, HW, C, w1, w2, act=None, want_y=True):
     """SELayer on h = act(x): returns (y = h * gate, pooled, relu(z1), gate)."""
     R = w1.shape[0]

@@ -797,6 +797,73 @@ def dwconv_bn_bwd(dy, x, act, w, dw_sink, dg_sink, db_sink, F, H, W, C, stride=1
     return torch.ops.ssl_mae.dwconv_bn_bwd(dy, x, *_act(act), w, dw_sink, dg_sink, db_sink, F, H, W, C, int(stride))
 
 
+@_op("dwconv_bn_bwd_dz", "(Tensor dy, Tensor x, Tensor bn_mean, Tensor bn_rstd, Tensor bn_w, Tensor bn_b, "
+                         "bool bn_gelu, Tensor w, Tensor(a!) dw_sink, Tensor(b!) dg_sink, Tensor(c!) db_sink, int F, "
+                         "int H, int W, int C, int stride=1) -> (Tensor, Tensor)", ("dw_sink", "dg_sink", "db_sink"))
+def _dwconv_bn_bwd_dz(dy, x, bm, br, bw, bb, bg, w, dw_sink, dg_sink, db_sink, F, H, W, C, stride=1):
+    return _K.dwconv_bn_bwd_dz(dy, x, (bm, br, bw, bb, bg), w, dw_sink, dg_sink, db_sink, F, H, W, C, stride)
+
+
+_dwconv_bn_bwd_dz.register_fake(lambda dy, x, *a: (torch.empty_like(x),
+                                                   x.new_empty((2, x.shape[-1]), dtype=torch.float32)))
+
+
+def dwconv_bn_bwd_dz(dy, x, act, w, dw_sink, dg_sink, db_sink, F, H, W, C, stride=1):
+    """dwconv_bn_bwd without the BatchNorm's dx pass: (dz, coef) for the folded expand gradients."""
+    return torch.ops.ssl_mae.dwconv_bn_bwd_dz(dy, x, *_act(act), w, dw_sink, dg_sink, db_sink, F, H, W, C,
+                                              int(stride))
+
+
+def _xbn(xbn):
+    return (None,) * 4 if xbn is None else tuple(xbn[:4])
+
+
+@_op("mbconv_fold_prep", "(Tensor coef, Tensor bn_mean, Tensor bn_rstd, Tensor bn_w, Tensor w, Tensor? x_mean, "
+                         "Tensor? x_rstd, Tensor? x_w, Tensor? x_b) -> (Tensor, Tensor, Tensor)")
+def _mbconv_fold_prep(coef, bm, br, bw, w, xm, xr, xw, xb):
+    return _K.mbconv_fold_prep(coef, bm, br, bw, w, None if xm is None else (xm, xr, xw, xb))
+
+
+@_mbconv_fold_prep.register_fake
+def _(coef, bm, br, bw, w, *a):
+    mid, cin = w.shape
+    return (w.new_empty((mid + cin, cin)), w.new_empty(cin, dtype=torch.float32),
+            w.new_empty((3, mid), dtype=torch.float32))
+
+
+def mbconv_fold_prep(coef, mean, rstd, gamma, w, xbn=None):
+    """[W'; -T], r0 and (omega, delta, c) of BN0's backward folded into the expand gradients."""
+    return torch.ops.ssl_mae.mbconv_fold_prep(coef, mean, rstd, gamma, w, *_xbn(xbn))
+
+
+@_op("mbconv_fold_dw", "(Tensor vec, Tensor w, Tensor P, Tensor G, Tensor s, int M, Tensor(a!) grad_sink, "
+                       "Tensor? x_mean, Tensor? x_rstd, Tensor? x_w, Tensor? x_b) -> ()", ("grad_sink",))
+def _mbconv_fold_dw(vec, w, P, G, s, M, grad_sink, xm, xr, xw, xb):
+    _K.mbconv_fold_dw(vec, w, P, G, s, M, grad_sink, None if xm is None else (xm, xr, xw, xb))
+
+
+_mbconv_fold_dw.register_fake(_none)
+
+
+def mbconv_fold_dw(vec, w, P, G, s, M, grad_sink, xbn=None):
+    """grad_sink += diag(omega) P - diag(delta) (w G) + c s^T (the folded expand weight gradient)."""
+    torch.ops.ssl_mae.mbconv_fold_dw(vec, w, P, G, s, int(M), grad_sink, *_xbn(xbn))
+    return grad_sink
+
+
+@_op("linear_dx2", "(Tensor a1, Tensor a2, Tensor w, Tensor? bias, Tensor? residual) -> Tensor")
+def _linear_dx2(a1, a2, w, bias, residual):
+    return _K.linear_dx2(a1, a2, w, bias, residual)
+
+
+_linear_dx2.register_fake(lambda a1, a2, w, *a: a1.new_empty((a1.shape[0], w.shape[1])))
+
+
+def linear_dx2(a1, a2, w, bias=None, residual=None):
+    """dx = [a1 | a2] @ w (+ bias) (+ residual): the data gradient over a two-buffer A operand."""
+    return torch.ops.ssl_mae.linear_dx2(a1, a2, w, bias, residual)
+
+
 # ============================================================================ SE
 @_op("se_fwd", "(Tensor x, int F, int HW, int C, Tensor w1, Tensor w2, Tensor? act_mean, Tensor? act_rstd, "
                "Tensor? act_w, Tensor? act_b, bool act_gelu) -> (Tensor, Tensor, Tensor, Tensor)")
