@@ -389,6 +389,48 @@ int sm_std(int dtype, const void* x, int64_t n, float* out, void* ws, int64_t ws
 int sm_segment_mean(int dtype, const void* x, int G, int R, int C, float* out, hipStream_t st);
 int sm_segment_mean_bwd(int dtype, const float* dy, int G, int R, int C, void* dx, hipStream_t st);
 
+/* ---- streaming dynamic inference (src/models/dynamic_infer.py; csrc/dynamic.hip), all fp32.
+ * clip = fp32 [B][C][T][H][W] read through its five element strides (no permute copy),
+ * 16-byte loads when sW == 1, W % 4 == 0 and the base and the other strides are 16-byte
+ * multiples, scalar loads otherwise (same pixel ownership and summation order: same bits).
+ *
+ * sm_motion_scores (dynamic_infer.py:34-49 motion_scores_l1): scores[b][0] = 0,
+ * scores[b][t] = mean over (c, h, w) of |x[b][c][t] - x[b][c][t-1]|; T == 1 gives zeros.
+ * One pass over the clip (a block walks t over a band of one (b, c) plane with the previous
+ * frame in registers); per-lane fp32 partials, wave reduce, then the per-wave partials summed
+ * in fp64 in a fixed order: deterministic, no atomics.  Workspace
+ * sm_motion_scores_workspace_bytes. */
+int64_t sm_motion_scores_workspace_bytes(int B, int C, int T, int H, int W);
+int sm_motion_scores(const float* clip, int B, int C, int T, int H, int W, int64_t sB, int64_t sC, int64_t sT,
+                     int64_t sH, int64_t sW, float* scores, void* ws, int64_t ws_bytes, hipStream_t st);
+/* dynamic_infer.py:66-71 (scores.topk(k).indices.sort()): idx int32 [B][k_eff], k_eff =
+ * min(k, T), the indices of the k_eff largest scores of each row in ascending index order.
+ * Where the reference leaves ties to torch.topk this defines them: among equal scores the
+ * lower frame index ranks first (-0 == +0), and NaN ranks after every number (NaNs among
+ * themselves by index).  T <= 256 and k >= 1, else -2. */
+int sm_topk_frames(const float* scores, int B, int T, int k, int32_t* idx, hipStream_t st);
+/* out fp32 dense [n][C][H][W], out[i] = clip[b_i][:, t_i] (dynamic_infer.py:80-81 torch.gather
+ * of the selected frames; :175 clip[:, :, t] of the samples still active):
+ * b_i = b_idx[i], or i / rows_per_b when b_idx is null; t_i = t_idx[i], or t_fixed when t_idx
+ * is null.  An index outside the clip yields a zero frame. */
+int sm_gather_frames(const float* clip, int B, int C, int T, int H, int W, int64_t sB, int64_t sC, int64_t sT,
+                     int64_t sH, int64_t sW, const int32_t* b_idx, int rows_per_b, const int32_t* t_idx,
+                     int t_fixed, int n, float* out, hipStream_t st);
+/* One frame's update + decision of streaming_early_exit (dynamic_infer.py:152-186), one block
+ * per active row i, s = active[i] (distinct, < B): if emb (fp32 [n][D], nullable) sum[s] +=
+ * emb[i], cnt[s] += 1; mean = sum[s] / max(cnt[s], 1); logits = w mean + bias (w [K][D], fixed
+ * reduction order); c = max softmax = 1 / sum_k exp(l_k - max l).  The sample is decided when
+ * final_pass (the reference's closing pass over the undecided, :180-186), or when c >= threshold
+ * and cnt[s] >= min_frames; a decided sample writes final_logits[s] [K], used[s] = cnt[s],
+ * conf[s] = c, decided[s] = 1.  State: sum [B][D], cnt int32 [B], decided uint8 [B],
+ * final_logits [B][K], used int32 [B], conf [B].  (D + K) * 4 bytes of LDS <= 64 KiB. */
+int sm_exit_step(const float* emb, const int32_t* active, int n, int B, int D, int K, const float* w,
+                 const float* bias, float threshold, int min_frames, int final_pass, float* sum, int32_t* cnt,
+                 uint8_t* decided, float* final_logits, int32_t* used, float* conf, hipStream_t st);
+/* The samples still undecided (the reference's ~decided mask, dynamic_infer.py:172, as an
+ * index list): active int32 [B] <- ascending s with decided[s] == 0, *count <- their number. */
+int sm_active_compact(const uint8_t* decided, int B, int32_t* active, int32_t* count, hipStream_t st);
+
 /* ---- optimizer (train_ssl_mae.py:163 AdamW, :87-89 GradScaler inf-skip) */
 int sm_nonfinite(const float* g, int64_t n, int* flag, hipStream_t st);
 /* p *= a (data-parallel gradient averaging after a SUM all-reduce) */

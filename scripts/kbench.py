@@ -2,6 +2,7 @@
 
 python scripts/kbench.py attn [--drop 0.1] [--iters 5]   # decoder (d=64) + encoder (d=32) attention
 python scripts/kbench.py gemm                              # the main GEMM shapes
+python scripts/kbench.py dynamic --batch 64               # motion scores, dense eval vs streaming early-exit
 Prints per-kernel-group average ms and TFLOP/s measured with HIP events.
 """
 import argparse
@@ -397,11 +398,89 @@ def bn0fold(args):
         rep("linear_dw da1", timeit(lambda: K.linear_dw(dz, x, sink), args.iters), T + t)
 
 
+def dynamic(args):
+    """Streaming dynamic inference at B clips of T x 112^2 (bf16 eval): the motion-score kernel
+    against the torch expression and the box's copy rate, then the dense VideoClassifier eval
+    forward (all B*T frames in one batch, the baseline) against streaming_early_exit with
+    nothing exiting, with about T/2 frames used on average, and the hybrid at k = T/2."""
+    import numpy as np
+    from ssl_mae_amd import dynamic_infer as DI
+    from ssl_mae_amd.finetune import VideoClassifier
+    from ssl_mae_amd.init_rule import apply_rule
+    dev = "cuda"
+    B, T, S, NC = args.batch, args.frames, 112, 101
+    g = torch.Generator().manual_seed(7)
+    clip = ((torch.rand(B, 3, T, S, S, generator=g) - 0.45) / 0.226
+            * (0.3 + 1.4 * torch.rand(B, 1, T, 1, 1, generator=g))).to(dev)
+    if args.only == "stream":   # the never-exit loop alone, for a rocprofv3 --kernel-trace --stats run
+        model = VideoClassifier(NC, img_size=S)
+        apply_rule(model)
+        model = model.to(dev).eval()
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+            t = timeit(lambda: DI.streaming_early_exit(model.backbone, model.classifier, clip, 2.0, min_frames=1),
+                       args.iters)
+        print(f"early exit, nothing exits: {t:8.2f} ms wall per call, {args.iters + 1} calls of {T} steps", flush=True)
+        return
+    gb = clip.numel() * 4 / 1e9
+    t_k = timeit(lambda: DI.motion_scores_l1(clip), args.iters * 4)
+    t_t = timeit(lambda: (clip[:, :, 1:] - clip[:, :, :-1]).abs().mean((1, 3, 4)), args.iters * 4)
+    dst = torch.empty_like(clip)
+    t_c = timeit(lambda: dst.copy_(clip), args.iters * 4)
+    del dst
+    ref = torch.zeros(B, T, device=dev)
+    ref[:, 1:] = (clip[:, :, 1:] - clip[:, :, :-1]).abs().mean((1, 3, 4))
+    err = float(((DI.motion_scores_l1(clip) - ref).abs() / ref.clamp_min(1e-30))[:, 1:].max())
+    print(f"motion_scores [B={B}, 3, T={T}, {S}, {S}] {gb:.3f} GB: kernel {t_k:7.3f} ms {gb / t_k * 1e3:7.1f} GB/s "
+          f"(clip bytes once) | torch expression {t_t:7.3f} ms {gb / t_t * 1e3:7.1f} GB/s ({t_t / t_k:.2f}x) | "
+          f"copy {t_c:7.3f} ms {2 * gb / t_c * 1e3:7.1f} GB/s read+write | max rel diff to torch {err:.1e}",
+          flush=True)
+
+    model = VideoClassifier(NC, img_size=S)
+    apply_rule(model)
+    model = model.to(dev).eval()
+    with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+        emb = model.backbone(clip)[1].view(B, T, -1)
+        full = emb.double().mean(1) @ model.classifier.weight.double().t()
+        model.classifier.weight.mul_(float(2.0 / full.std(dim=1).mean().clamp_min(1e-30)))
+        # the threshold whose dense prefix confidences give the average used frames nearest T/2
+        mean = emb.double().cumsum(1) / torch.arange(1, T + 1, device=dev, dtype=torch.float64)[None, :, None]
+        conf = torch.softmax(mean @ model.classifier.weight.double().t() + model.classifier.bias.double(), 2).amax(2)
+        conf = conf.cpu().numpy()
+
+        def avg_used(thr):
+            ok = conf >= thr
+            return float(np.where(ok.any(1), ok.argmax(1) + 1, T).mean())
+        cands = np.unique(conf)
+        thr_half = float(cands[int(np.argmin([abs(avg_used(c) - T / 2) for c in cands]))])
+
+        def dense():
+            return model(clip)
+
+        def stream(thr, c=clip):
+            return DI.streaming_early_exit(model.backbone, model.classifier, c, thr, min_frames=1)
+
+        def hybrid(thr):
+            return stream(thr, DI.select_topk_frames(clip, T // 2)[0])
+        t_d = timeit(dense, args.iters)
+        print(f"dense VideoClassifier eval (B*T = {B * T} frames, one batch): {t_d:8.2f} ms {B / t_d * 1e3:8.1f} clips/s",
+              flush=True)
+        for name, fn, thr in (("early exit, nothing exits (thr 2.0)", stream, 2.0),
+                              (f"early exit, thr {thr_half:.4f}", stream, thr_half),
+                              (f"hybrid k = {T // 2} (gating timed), thr {thr_half:.4f}", hybrid, thr_half)):
+            r0 = DI.readbacks()
+            used = fn(thr)[1].used_frames.float().mean().item()
+            rb = DI.readbacks() - r0
+            t = timeit(lambda: fn(thr), args.iters)
+            print(f"{name}: {t:8.2f} ms {B / t * 1e3:8.1f} clips/s ({t_d / t:.2f}x dense) | avg used frames "
+                  f"{used:.2f} (T / used = {T / used:.2f}) | {rb} readbacks per call", flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["attn", "gemm", "gemmk", "mbconv", "dw", "dwx", "dwse", "stem", "gemmw",
-                                     "bnstats", "dxgelu", "bn0fold"])
-    ap.add_argument("--batch", type=int, default=256)
+                                     "bnstats", "dxgelu", "bn0fold", "dynamic"])
+    ap.add_argument("--batch", type=int, default=256, help="clips (dynamic: 64 is the reported shape)")
+    ap.add_argument("--frames", type=int, default=16, help="dynamic: frames per clip")
     ap.add_argument("--drop", type=float, default=0.1)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--only", default="")
@@ -412,4 +491,4 @@ if __name__ == "__main__":
     from ssl_mae_amd.build import build
     build()
     {"attn": attn, "gemm": gemm, "gemmk": gemmk, "mbconv": mbconv, "dw": dw, "dwx": dwx, "dwse": dwse, "stem": stem, "gemmw": gemmw,
-     "bnstats": bnstats, "dxgelu": dxgelu, "bn0fold": bn0fold}[a.what](a)
+     "bnstats": bnstats, "dxgelu": dxgelu, "bn0fold": bn0fold, "dynamic": dynamic}[a.what](a)

@@ -995,3 +995,87 @@ def frames_normalize(frames, mean, std, bgr_swap=True, valid=None, out=None):
     call("sm_frames_normalize", ptr(frames), ptr(valid), B, T, H, W, ctypes.cast(m, ctypes.c_void_p),
          ctypes.cast(s, ctypes.c_void_p), 1 if bgr_swap else 0, ptr(out), stream())
     return out
+
+
+# ------------------------------------------------------------------ streaming dynamic inference
+def _clip5(clip):
+    _chk(clip)
+    if clip.dim() != 5 or clip.dtype != torch.float32:
+        raise _lib.KernelError("dynamic inference takes an fp32 [B,C,T,H,W] clip")
+    return tuple(clip.shape) + tuple(clip.stride())
+
+
+def _i32(t, n, what):
+    if t is None:
+        return
+    _chk(t)
+    if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < n:
+        raise _lib.KernelError(f"{what} must be a contiguous int32 tensor of at least {n} entries")
+
+
+def motion_scores(clip):
+    """clip fp32 [B,C,T,H,W] (any strides) -> fp32 [B,T] mean |frame t - frame t-1| (0 at t = 0)."""
+    args = _clip5(clip)
+    B, C, T, H, W = args[:5]
+    scores = torch.empty((B, T), dtype=torch.float32, device=clip.device)
+    nbytes = query("sm_motion_scores_workspace_bytes", B, C, T, H, W)
+    ws = _ws(nbytes, clip.device)
+    call("sm_motion_scores", ptr(clip), *args, ptr(scores), ptr(ws), nbytes, stream())
+    return scores
+
+
+def topk_frames(scores, k):
+    """scores fp32 [B,T] -> int32 [B, min(k,T)]: the top-k frames in ascending frame order
+    (ties: lower index first; NaN last)."""
+    _chk(scores)
+    if scores.dim() != 2 or scores.dtype != torch.float32 or not scores.is_contiguous():
+        raise _lib.KernelError("topk_frames takes contiguous fp32 [B,T] scores")
+    B, T = scores.shape
+    idx = torch.empty((B, min(int(k), T)), dtype=torch.int32, device=scores.device)
+    call("sm_topk_frames", ptr(scores), B, T, int(k), ptr(idx), stream())
+    return idx
+
+
+def gather_frames(clip, b_idx, t_idx, n, rows_per_b=1, t_fixed=0):
+    """-> dense fp32 [n,C,H,W], out[i] = clip[b_i, :, t_i]; b_i = b_idx[i] (int32) or
+    i // rows_per_b when b_idx is None, t_i = t_idx[i] or t_fixed when t_idx is None."""
+    args = _clip5(clip)
+    n = int(n)
+    _i32(b_idx, n, "b_idx")
+    _i32(t_idx, n, "t_idx")
+    C, H, W = args[1], args[3], args[4]
+    out = torch.empty((n, C, H, W), dtype=torch.float32, device=clip.device)
+    call("sm_gather_frames", ptr(clip), *args, ptr(b_idx), int(rows_per_b), ptr(t_idx), int(t_fixed), n, ptr(out),
+         stream())
+    return out
+
+
+def exit_step(emb, active, n, w, bias, threshold, min_frames, final, sum_emb, cnt, decided, final_logits, used, conf):
+    """One streaming early-exit update over the n samples active[:n] (state updated in place)."""
+    _chk(active, w, bias, sum_emb, cnt, decided, final_logits, used, conf, emb)
+    B, D = sum_emb.shape
+    K = w.shape[0]
+    n = int(n)
+    _i32(active, n, "active")
+    for t, dtype, shape, what in ((w, torch.float32, (K, D), "w"), (bias, torch.float32, (K,), "bias"),
+                                  (sum_emb, torch.float32, (B, D), "sum"), (cnt, torch.int32, (B,), "cnt"),
+                                  (decided, torch.uint8, (B,), "decided"),
+                                  (final_logits, torch.float32, (B, K), "final_logits"),
+                                  (used, torch.int32, (B,), "used"), (conf, torch.float32, (B,), "conf")):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.KernelError(f"exit_step: {what} must be contiguous {dtype} {shape}")
+    if emb is not None and (emb.dtype != torch.float32 or not emb.is_contiguous() or tuple(emb.shape) != (n, D)):
+        raise _lib.KernelError(f"exit_step: emb must be contiguous fp32 [{n},{D}]")
+    call("sm_exit_step", ptr(emb), ptr(active), n, B, D, K, ptr(w), ptr(bias), float(threshold), int(min_frames),
+         1 if final else 0, ptr(sum_emb), ptr(cnt), ptr(decided), ptr(final_logits), ptr(used), ptr(conf), stream())
+
+
+def active_compact(decided, active, count):
+    """active[:count] <- the ascending indices s with decided[s] == 0."""
+    _chk(decided, active, count)
+    B = decided.numel()
+    _i32(active, B, "active")
+    _i32(count, 1, "count")
+    if decided.dtype != torch.uint8 or not decided.is_contiguous():
+        raise _lib.KernelError("decided must be contiguous uint8 [B]")
+    call("sm_active_compact", ptr(decided), B, ptr(active), ptr(count), stream())

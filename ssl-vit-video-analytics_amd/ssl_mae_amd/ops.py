@@ -1296,6 +1296,73 @@ def frames_normalize(frames, mean, std, bgr_swap=True, valid=None):
                                               bool(bgr_swap), valid)
 
 
+# ============================================================================ streaming dynamic inference
+@_op("motion_scores", "(Tensor clip) -> Tensor")
+def _motion_scores(clip):
+    return _K.motion_scores(clip)
+
+
+_motion_scores.register_fake(lambda clip: clip.new_empty((clip.shape[0], clip.shape[2]), dtype=torch.float32))
+
+
+def motion_scores(clip):
+    return torch.ops.ssl_mae.motion_scores(clip)
+
+
+@_op("topk_frames", "(Tensor scores, int k) -> Tensor")
+def _topk_frames(scores, k):
+    return _K.topk_frames(scores, k)
+
+
+_topk_frames.register_fake(lambda scores, k: scores.new_empty((scores.shape[0], min(k, scores.shape[1])),
+                                                              dtype=torch.int32))
+
+
+def topk_frames(scores, k):
+    return torch.ops.ssl_mae.topk_frames(scores, int(k))
+
+
+@_op("gather_frames", "(Tensor clip, Tensor? b_idx, Tensor? t_idx, int n, int rows_per_b, int t_fixed) -> Tensor")
+def _gather_frames(clip, b_idx, t_idx, n, rows_per_b, t_fixed):
+    return _K.gather_frames(clip, b_idx, t_idx, n, rows_per_b, t_fixed)
+
+
+_gather_frames.register_fake(lambda clip, b_idx, t_idx, n, rows_per_b, t_fixed: clip.new_empty(
+    (n, clip.shape[1], clip.shape[3], clip.shape[4]), dtype=torch.float32))
+
+
+def gather_frames(clip, b_idx, t_idx, n, rows_per_b=1, t_fixed=0):
+    return torch.ops.ssl_mae.gather_frames(clip, b_idx, t_idx, int(n), int(rows_per_b), int(t_fixed))
+
+
+@_op("exit_step", "(Tensor? emb, Tensor active, int n, Tensor w, Tensor bias, float threshold, int min_frames, "
+                  "bool final, Tensor(a!) sum, Tensor(b!) cnt, Tensor(c!) decided, Tensor(d!) final_logits, "
+                  "Tensor(e!) used, Tensor(f!) conf) -> ()", ("sum", "cnt", "decided", "final_logits", "used", "conf"))
+def _exit_step(emb, active, n, w, bias, threshold, min_frames, final, sum, cnt, decided, final_logits, used, conf):
+    _K.exit_step(emb, active, n, w, bias, threshold, min_frames, final, sum, cnt, decided, final_logits, used, conf)
+
+
+_exit_step.register_fake(_none)
+
+
+def exit_step(emb, active, n, w, bias, threshold, min_frames, final, sum_emb, cnt, decided, final_logits, used,
+              conf):
+    torch.ops.ssl_mae.exit_step(emb, active, int(n), w, bias, float(threshold), int(min_frames), bool(final),
+                                sum_emb, cnt, decided, final_logits, used, conf)
+
+
+@_op("active_compact", "(Tensor decided, Tensor(a!) active, Tensor(b!) count) -> ()", ("active", "count"))
+def _active_compact(decided, active, count):
+    _K.active_compact(decided, active, count)
+
+
+_active_compact.register_fake(_none)
+
+
+def active_compact(decided, active, count):
+    torch.ops.ssl_mae.active_compact(decided, active, count)
+
+
 def registered_ops():
     """Names of every ssl_mae operator registered by this module."""
     return sorted(n for n in dir(torch.ops.ssl_mae) if not n.startswith("_") and
