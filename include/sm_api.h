@@ -44,15 +44,15 @@ int sm_gemm(int ab_dtype, int c_dtype, int a_layout, int b_layout, int M, int N,
  * forward / data-gradient Linear of the step): 1 = persistent blocks with each tile's
  * output stores drained under the next tile's K loop (default), 0 = one tile per block.
  * Outputs are bit-identical either way.  mode < 0 only queries.  Returns the previous mode.
- * (= sm_gemm_tuning key 1.) */
+ * (= sm_gemm_tuning key 0.) */
 int sm_gemm_persistent(int mode);
 /* GEMM dispatch tuning for A/B measurement scripts (never changed by the product path):
- * key 0 tile variant (0 = per-shape rule, 1-3 pinned), 1 persistent form on/off,
- * 2 / 3 persistent form's minimum N / maximum K at K > 128, 4 tiles per persistent block
- * (-1 = per-K rule, 0 = fully persistent), 5 / 6 tiles per block at K <= 128 / above,
- * 7 minimum K per block for the v_mfma_f32_16x16x32_bf16 K loop of K-major-A tiles
- * (default 1 << 30 = off: measured neutral), 8 the 384 x 128 pipelined weight-gradient tile
- * (gemm_dw384) for outputs it divides (default 1 = on), 9 keep such outputs untransposed in
+ * key 0 persistent form on/off,
+ * 1 / 2 persistent form's minimum N / maximum K at K > 128, 3 tiles per persistent block
+ * (-1 = per-K rule, 0 = fully persistent), 4 / 5 tiles per block at K <= 128 / above,
+ * 6 minimum K per block for the v_mfma_f32_16x16x32_bf16 K loop of K-major-A tiles
+ * (default 1 << 30 = off: measured neutral), 7 the 384 x 128 pipelined weight-gradient tile
+ * (gemm_dw384) for outputs it divides (default 1 = on), 8 keep such outputs untransposed in
  * sm_linear_dw_bias (fused bias gradient; default 1).
  * *prev <- the current value; set > 0 stores value, set < 0 restores the default.
  * Returns 0, or -2 for an unknown key.  Host-side only (no launch). */

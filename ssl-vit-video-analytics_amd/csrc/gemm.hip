@@ -10,11 +10,11 @@
 // Linear dX   dX = dY W      : (a 0, b 1)
 // Linear dW   dW = dY^T X    : (a 1, b 1)   -> split-K over the token axis
 //
-// bf16 path (gemm_bf16_kernel; gemm_bf16_v2 below is the default, see there):
-// 128x128x64 block tile, 4 waves (2x2), each wave 64x64 = 2x2
+// bf16 path (gemm_bf16_v2, see there; gemm_bf16_pp and gemm_dw384 are its persistent and
+// weight-gradient forms): BM x 128 x 64 block tile, each wave 64x64 = 2x2
 // v_mfma_f32_32x32x16_bf16 tiles.  K-contiguous operands are staged to an
 // XOR-swizzled [row][64] LDS image read with ds_read_b128; M/N-contiguous operands
-// are staged as a [k][128] image and read with ds_read_b64_tr_b16 (hardware
+// are staged as a [k][rows] image and read with ds_read_b64_tr_b16 (hardware
 // transpose), so no operand ever needs a transposed copy in HBM.  Register-staged
 // prefetch of tile k+1 is issued before the MFMAs of tile k (async-STAGE split).
 // f32 path (parity mode): 64x64x16 tile on v_mfma_f32_32x32x2_f32 (exact fp32).
@@ -95,70 +95,11 @@ SM_DEV void epilogue_store(const GemmArgs& g, int64_t row, int col, float acc, i
   C[idx] = from_f<TC>(v);
 }
 
-// ============================================================ bf16 MFMA kernel
-constexpr int BM = 128, BN = 128, BKT = 64;
+// ============================================================ bf16 MFMA kernels: shared pieces
+constexpr int BKT = 64;   // K-step of every bf16 kernel
 
 // byte offset inside a K-major [rows][64] bf16 tile (128-B rows, 16-B chunks swizzled)
 SM_DEV int kmaj_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-// byte offset inside an MN-major [64][128] bf16 tile (256-B rows)
-SM_DEV int mnmaj_off(int krow, int col) {
-  return krow * 256 + ((((col >> 3) ^ ((krow & 3) << 2))) << 4) + ((col & 7) << 1);
-}
-
-template <bool KMAJ>
-SM_DEV void gload_tile(const __bf16* base, int64_t ld, int rows_total, int row0, int k0, int kend,
-                       uint4 (&r)[4]) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = t + 256 * i;
-    int row, kk;
-    if (KMAJ) { row = c >> 3; kk = (c & 7) * 8; }       // [row][k] chunks
-    else      { kk = c >> 4; row = (c & 15) * 8; }      // [k][row] chunks
-    const int gr = row0 + row, gk = k0 + kk;
-    bool ok = KMAJ ? (gr < rows_total && gk < kend) : (gk < kend && gr < rows_total);
-    if (ok) {
-      const __bf16* p = KMAJ ? base + (int64_t)gr * ld + gk : base + (int64_t)gk * ld + gr;
-      r[i] = *(const uint4*)p;
-    } else {
-      r[i] = make_uint4(0, 0, 0, 0);
-    }
-  }
-}
-
-template <bool KMAJ>
-SM_DEV void lstore_tile(char* lds, const uint4 (&r)[4]) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = t + 256 * i;
-    int off;
-    if (KMAJ) off = kmaj_off(c >> 3, c & 7);
-    else      off = mnmaj_off(c >> 4, (c & 15) * 8);
-    *(uint4*)(lds + off) = r[i];
-  }
-}
-
-// Fragment for 32 rows (row base rb inside the tile) at k-substep s (16 k values).
-template <bool KMAJ>
-SM_DEV bf16x8 lread_frag(const char* lds, int rb, int s) {
-  const int l = threadIdx.x & 63;
-  if (KMAJ) {
-    const int row = rb + (l & 31);
-    const int chunk = 2 * s + (l >> 5);
-    return *(const bf16x8*)(lds + kmaj_off(row, chunk));
-  } else {
-    const int h = l >> 5, g1 = (l >> 4) & 1, i = l & 15, q = i >> 2, p = i & 3;
-    const int col = rb + 16 * g1 + 4 * p;
-    const int k0 = 16 * s + 8 * h + q;
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lds + mnmaj_off(k0, col)));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lds + mnmaj_off(k0 + 4, col)));
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
-  }
-}
 
 // Row-staged stores (gemm_bf16_v2).  A row run is 8 consecutive columns of one output
 // row held by one lane; stored straight from the lanes, a store instruction covers 32
@@ -490,69 +431,6 @@ SM_DEV __attribute__((always_inline)) void gemm_epilogue(const GemmArgs& g, f32x
 // ring of 32-K stages, no staging registers or ds_write, one barrier per stage -- gave
 // bit-identical outputs 4-40 % slower on every K-major forward and data-gradient shape of
 // the step, profiles/r04d_gemm_dma_ab_and_ksweep.txt; removed.)
-// One 128x128 output tile per block; 1-D grid over (m-tile, n-tile) with an
-// XCD-aware bijective remap: the n-tiles of one m-tile (which share the A panel)
-// are dispatched to the same XCD's L2.  (A persistent variant that prefetched the
-// next tile's first K-step under the epilogue measured 5-20 % slower: with three
-// resident blocks per CU the hardware already overlaps one block's epilogue with
-// another's prologue.)
-template <bool AK, bool BK, typename TC, bool VEC>
-__global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmArgs g) {
-  __shared__ __attribute__((aligned(16))) char lds[2 * BM * BKT * 2];
-  char* la = lds;
-  char* lb = lds + BM * BKT * 2;
-  const int ntn = (g.N + BN - 1) / BN;
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int m0 = (tile / ntn) * BM, n0 = (tile % ntn) * BN;
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  const int wm = (w >> 1) * 64, wn = (w & 1) * 64;
-  const __bf16* A = (const __bf16*)g.A;
-  const __bf16* B = (const __bf16*)g.B;
-  const int kb = g.k_begin + blockIdx.z * g.k_chunk;
-  const int ke = min(g.K, kb + g.k_chunk);
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  uint4 ra[4], rb[4];
-  if (kb < ke) {
-    gload_tile<AK>(A, g.lda, g.M, m0, kb, ke, ra);
-    gload_tile<BK>(B, g.ldb, g.N, n0, kb, ke, rb);
-  }
-  for (int k0 = kb; k0 < ke; k0 += BKT) {
-    lstore_tile<AK>(la, ra);
-    lstore_tile<BK>(lb, rb);
-    __syncthreads();
-    if (k0 + BKT < ke) {
-      gload_tile<AK>(A, g.lda, g.M, m0, k0 + BKT, ke, ra);
-      gload_tile<BK>(B, g.ldb, g.N, n0, k0 + BKT, ke, rb);
-    }
-#pragma unroll
-    for (int s = 0; s < BKT / 16; ++s) {
-      bf16x8 af[2], bfr[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) af[i] = lread_frag<AK>(la, wm + 32 * i, s);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) bfr[j] = lread_frag<BK>(lb, wn + 32 * j, s);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
-    }
-    __syncthreads();
-  }
-  gemm_epilogue<TC, VEC>(g, acc, m0, n0, wm, wn, l, blockIdx.z);
-}
-
 // ============================================================ bf16 MFMA kernel, v2
 // BM x 128 block tile, BK = 64, each wave 64 x 64 (2 x 2 v_mfma_f32_32x32x16_bf16):
 // BM = 256 -> 8 waves (4 along M x 2 along N, 512 threads), BM = 128 -> 4 waves.
@@ -560,8 +438,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmArgs g) {
 // voffsets computed once, the K advance moves the wave-uniform base of the buffer
 // descriptor, and rows / columns past the matrix or the K tail read as zero through
 // an out-of-range voffset.  The main loop therefore carries no per-step address
-// arithmetic in VGPRs (the first kernel spent ~10 VALU instructions per MFMA on 64-bit
-// pointer updates and zero-fill moves), which frees the registers for 4 waves per
+// arithmetic in VGPRs (staging through 64-bit pointers spent ~10 VALU instructions per MFMA
+// on pointer updates and zero-fill moves), which frees the registers for 4 waves per
 // SIMD at BM = 256.
 constexpr uint32_t BUF_OOB = 0x40000000u;   // >= num_records: the load returns 0
 constexpr int XA_MAXK = 1536;                // IMP 6: channels of the transformed A operand
@@ -1913,31 +1791,55 @@ __global__ void splitk_reduce_kernel(GemmArgs g, int splits) {
   }
 }
 
-int variant_bm(int v);
-int variant_bn(int v);
-int gemm_variant(int M, int N, int K);
+// ============================================================ host: tile choice, split-K, launches
+// Tuning knobs (A/B measurement runs only; scripts/ set them through sm_gemm_tuning, the
+// product path never changes them).  Defaults are the measured best per shape family.
+enum { TUNE_PP = 0, TUNE_PP_MINN = 1, TUNE_PP_MAXK = 2, TUNE_PP_ROUNDS = 3, TUNE_PP_ROUNDS_SMALLK = 4,
+       TUNE_PP_ROUNDS_MIDK = 5, TUNE_MF16_MINK = 6, TUNE_DW384 = 7, TUNE_DW384_NOTR = 8, TUNE_COUNT = 9 };
+constexpr int kMF16Off = 1 << 30;
+constexpr int kTuneDefault[TUNE_COUNT] = {1, 128, 6 * BKT, -1, 8, 2, kMF16Off, 1, 1};
+int g_tune[TUNE_COUNT] = {1, 128, 6 * BKT, -1, 8, 2, kMF16Off, 1, 1};
 
-// Resident blocks of a bf16 variant on the whole device (occupancy query of the
-// split-K instantiation, cached; 2 / 4 blocks per CU x 256 CUs without a device).
-int gemm_slots(int v) {
-  static int cache[4] = {0, 0, 0, 0};
-  const int vi = v == 2 ? 2 : 3;
-  if (cache[vi]) return cache[vi];
-  int dev = 0, cus = 0, per = 0;
-  if (hipGetDevice(&dev) == hipSuccess &&
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) {
-    const hipError_t e =
-        vi == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, gemm_bf16_v2<false, false, float, true, 256>, 512, 0)
-                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, gemm_bf16_v2<false, false, float, true, 128>, 256, 0);
-    if (e != hipSuccess) per = 0;
-  }
-  if (cus <= 0 || per <= 0) {
-    (void)hipGetLastError();
-    cus = 256;
-    per = vi == 2 ? 2 : 4;
-  }
-  cache[vi] = cus * per;
-  return cache[vi];
+// Block rows BM of the gemm_bf16_v2 tile: 256 (8 waves) when M >= 192, else 128 (4 waves; a
+// 256-row tile half empty loses to BM = 128 there: dW of the 96-channel MBConv projection).
+// Measured and dropped (round 2): a 256 x 256 tile on 8 waves of 128 x 64 (0.75 KB of
+// fragment reads and 256 B of LDS-DMA staging per MFMA instead of v2's 1 KB + 384 B),
+// double-buffered buffer -> LDS DMA, one block per CU: 20-30 % slower than v2 on every
+// weight gradient of the step (profiles/r02g/dw_wide.txt).  Its operand delivery per CU
+// (64 KB in flight, ~21 GB/s) is the bound, not the LDS; v2's two resident blocks keep
+// 96 KB in flight.
+int gemm_variant(int M, int N) {
+  // 384-row weight gradients with narrow rows (dW [384][384], [384][96]): three full
+  // 128-row tiles instead of two 256-row tiles, one a quarter empty -- measured
+  // 0.86 -> 0.79 ms and 5.18 -> 4.45 ms; wider (N = 1536) and 192-row ones are faster at
+  // BM = 256 (profiles/r02q/dw_bm_ab.txt)
+  if (M == 384 && N <= 384) return 128;
+  return M >= 192 ? 256 : 128;
+}
+// v2's grid for an M x N output: BM x 128 tiles
+int64_t v2_tiles(int M, int N, int bm) { return (int64_t)((M + bm - 1) / bm) * ((N + 127) / 128); }
+
+// Blocks of KERNEL (THREADS per block) resident on the whole device: CUs x the occupancy query,
+// cached; 256 CUs x PER_FALLBACK blocks without a device.
+template <auto KERNEL, int THREADS, int PER_FALLBACK>
+int resident_blocks() {
+  static const int blocks = [] {
+    int dev = 0, cus = 0, per = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, KERNEL, THREADS, 0) != hipSuccess || cus <= 0 || per <= 0) {
+      (void)hipGetLastError();
+      cus = 256;
+      per = PER_FALLBACK;
+    }
+    return cus * per;
+  }();
+  return blocks;
+}
+// v2 at BM = bm (the split-K instantiation)
+int gemm_slots(int bm) {
+  return bm == 256 ? resident_blocks<gemm_bf16_v2<false, false, float, true, 256>, 512, 2>()
+                   : resident_blocks<gemm_bf16_v2<false, false, float, true, 128>, 256, 4>();
 }
 
 // Split-K over a long reduction (weight gradients: K = tokens).  bf16: the split count
@@ -1948,10 +1850,9 @@ int gemm_slots(int v) {
 // split's tiles sharing a token range dealt consecutively in groups of <= 8 -- measured
 // 0-16 % slower than this split-major order on every weight gradient.)
 int choose_splits(int M, int N, int K, bool bf16) {
-  const int v = gemm_variant(M, N, K);
-  const int bm = bf16 ? variant_bm(v) : FBM, bn = bf16 ? variant_bn(v) : FBN, bk = bf16 ? BKT : FBK;
+  const int bm = bf16 ? gemm_variant(M, N) : FBM, bn = bf16 ? 128 : FBN, bk = bf16 ? BKT : FBK;
   const int64_t tiles = (int64_t)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-  const int64_t slots = bf16 ? gemm_slots(v) : 512;
+  const int64_t slots = bf16 ? gemm_slots(bm) : 512;
   if (tiles >= slots || K < 4096) return 1;
   // two rounds: 2-16 rounds measured the same time (profiles/r04f_dw_rounds.txt; the A/B knob
   // that pinned the count, and so the reduction order, is gone: results stay reproducible)
@@ -1963,37 +1864,41 @@ int choose_splits(int M, int N, int K, bool bf16) {
   return s < 1 ? 1 : (int)s;
 }
 
-// bf16 kernel variant: 1 = gemm_bf16_kernel (128 x 128, 4 waves), 2 = gemm_bf16_v2 at
-// BM = 256 (8 waves), 3 = gemm_bf16_v2 at BM = 128.  Default (0): v2, BM = 256 when
-// M >= 192 (a 256-row tile half empty loses to BM = 128 there: dW of the 96-channel
-// MBConv projection).  sm_gemm_tuning(TUNE_VARIANT) pins one (A/B measurement runs).
-// Measured and dropped (round 2): a 256 x 256 tile on 8 waves of 128 x 64 (0.75 KB of
-// fragment reads and 256 B of LDS-DMA staging per MFMA instead of v2's 1 KB + 384 B),
-// double-buffered buffer -> LDS DMA, one block per CU: 20-30 % slower than v2 on every
-// weight gradient of the step (profiles/r02g/dw_wide.txt).  Its operand delivery per CU
-// (64 KB in flight, ~21 GB/s) is the bound, not the LDS; v2's two resident blocks keep
-// 96 KB in flight.
-// Tuning knobs (A/B measurement runs only; scripts/ set them through sm_gemm_tuning, the
-// product path never changes them).  Defaults are the measured best per shape family.
-enum { TUNE_VARIANT = 0, TUNE_PP = 1, TUNE_PP_MINN = 2, TUNE_PP_MAXK = 3, TUNE_PP_ROUNDS = 4,
-       TUNE_PP_ROUNDS_SMALLK = 5, TUNE_PP_ROUNDS_MIDK = 6, TUNE_MF16_MINK = 7, TUNE_DW384 = 8,
-       TUNE_DW384_NOTR = 9, TUNE_COUNT = 10 };
-constexpr int kMF16Off = 1 << 30;
-constexpr int kTuneDefault[TUNE_COUNT] = {0, 1, 128, 6 * BKT, -1, 8, 2, kMF16Off, 1, 1};
-int g_tune[TUNE_COUNT] = {0, 1, 128, 6 * BKT, -1, 8, 2, kMF16Off, 1, 1};
-int gemm_variant(int M, int N, int K) {
-  const int forced = (g_tune[TUNE_VARIANT] >= 1 && g_tune[TUNE_VARIANT] <= 3) ? g_tune[TUNE_VARIANT] : 0;
-  if (forced) return forced;
-  // 384-row weight gradients with narrow rows (dW [384][384], [384][96]): three full
-  // 128-row tiles instead of two 256-row tiles, one a quarter empty -- measured
-  // 0.86 -> 0.79 ms and 5.18 -> 4.45 ms; wider (N = 1536) and 192-row ones are faster at
-  // BM = 256 (profiles/r02q/dw_bm_ab.txt)
-  if (M == 384 && N <= 384) return 3;
-  return M >= 192 ? 2 : 3;
-  (void)K;
+// The split-K plan of g (M, N, K set): `want` splits of K in chunks that are multiples of kstep
+// (BKT / FBK), their fp32 slabs [split][M][N] in ws.  Fills g.k_begin, g.k_chunk and g.partial
+// and returns the split count the chunk rounding leaves (<= want): the grid's z extent and the
+// reduce's slab count.  One split, no slabs, when want <= 1, the reduction is empty (K <= 0:
+// C = beta*C + bias, epilogue only) or ws cannot hold `want` slabs.
+int plan_splitk(GemmArgs& g, int want, int kstep, void* ws, int64_t ws_bytes) {
+  g.k_begin = 0;
+  g.k_chunk = g.K > 0 ? g.K : 0;
+  g.partial = nullptr;
+  if (want <= 1 || g.K <= 0 || ws == nullptr || ws_bytes < (int64_t)want * g.M * g.N * 4) return 1;
+  int64_t chunk = ((int64_t)g.K + want - 1) / want;
+  chunk = (chunk + kstep - 1) / kstep * kstep;
+  g.k_chunk = (int)chunk;
+  g.partial = (float*)ws;
+  return (int)((g.K + chunk - 1) / chunk);
 }
-int variant_bm(int v) { return v == 2 ? 256 : 128; }
-int variant_bn(int v) { return 128; (void)v; }
+
+// slabs -> C through the elementwise epilogue (nothing to do for one split)
+template <typename TC>
+void launch_splitk_reduce(const GemmArgs& g, int splits, hipStream_t st) {
+  if (splits <= 1) return;
+  const int64_t total = (int64_t)g.M * g.N;
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(splitk_reduce_kernel<TC>, dim3(blocks), dim3(256), 0, st, g, splits);
+}
+
+// gemm_bf16_v2 on g: BM from gemm_variant, one block per (split, tile)
+template <bool AK, bool BK, typename TC, bool VEC, int IMP>
+void launch_v2(const GemmArgs& g, int splits, hipStream_t st) {
+  const int bm = gemm_variant(g.M, g.N);
+  const dim3 grid((unsigned)(v2_tiles(g.M, g.N, bm) * splits));
+  if (bm == 256) hipLaunchKernelGGL((gemm_bf16_v2<AK, BK, TC, VEC, 256, IMP>), grid, dim3(512), 0, st, g);
+  else hipLaunchKernelGGL((gemm_bf16_v2<AK, BK, TC, VEC, 128, IMP>), grid, dim3(256), 0, st, g);
+}
 
 // Persistent pipelined form (gemm_bf16_pp) for a non-split bf16 GEMM with a K-major A at
 // BM = 256 whose epilogue has no side output: used when the grid would take more than one
@@ -2013,18 +1918,22 @@ bool pp_enabled() { return g_tune[TUNE_PP] != 0; }
 // K = 384 the data gradient still loses 2-4 %, the forward gains 1-2.5 % (not taken;
 // profiles/r06y_pp_minn_ab.txt).  The minimum N is now 128 (two n-tiles: N = 96 keeps one tile
 // per block, see above).
-bool pp_ok(const GemmArgs& g) {
-  return pp_enabled() && g.partial == nullptr && g.colsum == nullptr && !g.ctrans && !(g.epi & 4) &&
-         (!((g.epi & 1) && g.aux) || (g.beta == 0.f && g.row_scale == nullptr)) && g.aux_out == nullptr &&
+// This shape rule on a whole, unsplit BM = 256 product with the plain store:
+bool pp_shape_ok(const GemmArgs& g) {
+  return pp_enabled() && gemm_variant(g.M, g.N) == 256 && g.partial == nullptr && g.colsum == nullptr && !g.ctrans &&
          g.K > 0 && g.k_begin == 0 && g.k_chunk >= g.K &&
          (g.K <= 2 * BKT || (g.K <= g_tune[TUNE_PP_MAXK] && g.N >= g_tune[TUNE_PP_MINN]));
 }
-// the GELU-backward data gradient, with or without the activation side output (IMP 9), in the
-// persistent form: the same shape rule, no bias / residual / row scale in its epilogue
+// forward epilogues: no GELU backward or activation side output; the GELU pre-activation side
+// output (IMP 13) only without residual / row scale
+bool pp_ok(const GemmArgs& g) {
+  return pp_shape_ok(g) && !(g.epi & 4) && g.aux_out == nullptr &&
+         (!((g.epi & 1) && g.aux) || (g.beta == 0.f && g.row_scale == nullptr));
+}
+// the GELU-backward data gradient, with or without the activation side output (IMP 9): no
+// bias / residual / row scale in its epilogue
 bool pp_ok_gelu_bwd(const GemmArgs& g) {
-  return pp_enabled() && g.partial == nullptr && g.colsum == nullptr && !g.ctrans && g.epi == 4 && g.aux &&
-         g.bias == nullptr && g.beta == 0.f && g.row_scale == nullptr && g.K > 0 && g.k_begin == 0 &&
-         g.k_chunk >= g.K && (g.K <= 2 * BKT || (g.K <= g_tune[TUNE_PP_MAXK] && g.N >= g_tune[TUNE_PP_MINN]));
+  return pp_shape_ok(g) && g.epi == 4 && g.aux && g.bias == nullptr && g.beta == 0.f && g.row_scale == nullptr;
 }
 int pp_rounds(const GemmArgs& g) {
   const int forced = g_tune[TUNE_PP_ROUNDS];   // A/B runs; 0 = fully persistent
@@ -2035,23 +1944,13 @@ int pp_rounds(const GemmArgs& g) {
 // weight gradients -- and in gemm_bf16_pp the 16x16x32 loop's four A fragments spill 11-36
 // VGPRs at the 128-register cap of two 8-wave blocks per CU: not built.)
 bool mf16_ok(const GemmArgs& g) { return (g.k_chunk < g.K ? g.k_chunk : g.K) >= g_tune[TUNE_MF16_MINK]; }
+// false: one round of resident blocks or less -- the caller launches the one-tile-per-block form
 template <bool BK, int IMP>
 bool launch_pp(const GemmArgs& g, hipStream_t st) {
-  static int slots = 0;   // resident blocks on the device, a multiple of 8 (occupancy query, cached)
-  if (slots == 0) {
-    int dev = 0, cus = 0, per = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, gemm_bf16_pp<BK, IMP>, 512, 0) != hipSuccess) {
-      (void)hipGetLastError();
-      cus = 256;
-      per = 2;
-    }
-    slots = (cus * (per > 0 ? per : 1)) & ~7;
-    if (slots < 8) slots = 8;
-  }
-  const int64_t tiles = (int64_t)((g.N + 127) / 128) * ((g.M + 255) / 256);
-  if (tiles <= slots) return false;   // one round: the one-tile-per-block form
+  int slots = resident_blocks<gemm_bf16_pp<BK, IMP>, 512, 2>() & ~7;   // the grid is a multiple of 8
+  if (slots < 8) slots = 8;
+  const int64_t tiles = v2_tiles(g.M, g.N, 256);
+  if (tiles <= slots) return false;
   // at most R = pp_rounds() tiles per block (grid 8 ceil(T / 8 / R), at least one resident round)
   const int rounds = pp_rounds(g);
   int64_t grid = slots;
@@ -2063,21 +1962,15 @@ bool launch_pp(const GemmArgs& g, hipStream_t st) {
   return true;
 }
 
-// split count for gemm_dw384 (one block per CU): the largest R <= 2 whole rounds of the CUs that
-// stays within the v2 split count the caller's workspace was sized for
+// gemm_dw384 (one block per CU) where it divides an M x N weight gradient that v2 would split
+// s_v2 ways: its split count is the largest R <= 2 whole rounds of the CUs that stays within
+// s_v2, the count the caller's workspace was sized for
+bool dw384_ok(int M, int N) { return g_tune[TUNE_DW384] && M % DW3_BM == 0 && N % DW3_BN == 0; }
 int dw384_splits(int M, int N, int s_v2) {
-  if (!g_tune[TUNE_DW384] || M % DW3_BM || N % DW3_BN || s_v2 <= 1) return s_v2;
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-      (void)hipGetLastError();
-      cus = 256;
-    }
-  }
+  if (!dw384_ok(M, N) || s_v2 <= 1) return s_v2;
   const int tiles = (M / DW3_BM) * (N / DW3_BN);
   for (int r = 2; r >= 1; --r) {
-    const int sr = r * cus / tiles;
+    const int sr = r * resident_blocks<gemm_dw384<false>, 512, 1>() / tiles;
     if (sr >= 2 && sr <= s_v2) return sr;
   }
   return s_v2;
@@ -2085,19 +1978,15 @@ int dw384_splits(int M, int N, int s_v2) {
 template <bool AK, bool BK, typename TC, bool VEC>
 void launch_bf16(const GemmArgs& g, int splits, hipStream_t st) {
   if constexpr (!AK && !BK && sizeof(TC) == 4 && VEC) {
-    // weight gradients on the 384 x 128 pipelined tile (gemm_dw384) where it divides the output
-    if (g_tune[TUNE_DW384] && g.M % DW3_BM == 0 && g.N % DW3_BN == 0 && g.partial != nullptr) {
+    if (dw384_ok(g.M, g.N) && g.partial != nullptr) {   // split weight gradients on the 384 x 128 pipelined tile
       const int t384 = (g.N / DW3_BN) * (g.M / DW3_BM);
       if (g.colsum) hipLaunchKernelGGL((gemm_dw384<true>), dim3(t384 * splits), dim3(512), 0, st, g);
       else hipLaunchKernelGGL((gemm_dw384<false>), dim3(t384 * splits), dim3(512), 0, st, g);
       return;
     }
   }
-  const int v = gemm_variant(g.M, g.N, g.K);
-  const int bm = variant_bm(v), bn = variant_bn(v);
-  const int tiles = ((g.N + bn - 1) / bn) * ((g.M + bm - 1) / bm);
   if constexpr (AK && VEC && sizeof(TC) == 2) {
-    if (v == 2 && splits == 1 && pp_ok(g)) {
+    if (splits == 1 && pp_ok(g)) {
       if ((g.epi & 1) && g.aux) {   // fc1: GELU + pre-activation side output
         if (launch_pp<BK, 13>(g, st)) return;
       } else if (launch_pp<BK, 0>(g, st)) {
@@ -2105,11 +1994,14 @@ void launch_bf16(const GemmArgs& g, int splits, hipStream_t st) {
       }
     }
   }
-  if (v == 1) hipLaunchKernelGGL((gemm_bf16_kernel<AK, BK, TC, VEC>), dim3(tiles, 1, splits), dim3(256), 0, st, g);
-  else if (AK && v == 2 && mf16_ok(g))
-    hipLaunchKernelGGL((gemm_bf16_v2<AK, BK, TC, VEC, 256, 0, 128, AK ? 16 : 32>), dim3(tiles * splits), dim3(512), 0, st, g);
-  else if (v == 2) hipLaunchKernelGGL((gemm_bf16_v2<AK, BK, TC, VEC, 256>), dim3(tiles * splits), dim3(512), 0, st, g);
-  else hipLaunchKernelGGL((gemm_bf16_v2<AK, BK, TC, VEC, 128>), dim3(tiles * splits), dim3(256), 0, st, g);
+  if constexpr (AK) {
+    if (gemm_variant(g.M, g.N) == 256 && mf16_ok(g)) {   // A/B runs only: TUNE_MF16_MINK is off by default
+      const dim3 grid((unsigned)(v2_tiles(g.M, g.N, 256) * splits));
+      hipLaunchKernelGGL((gemm_bf16_v2<AK, BK, TC, VEC, 256, 0, 128, 16>), grid, dim3(512), 0, st, g);
+      return;
+    }
+  }
+  launch_v2<AK, BK, TC, VEC, 0>(g, splits, st);
 }
 
 template <bool AK, bool BK>
@@ -2132,24 +2024,28 @@ int launch_layout(int abt, int ct, GemmArgs g, int splits, hipStream_t st) {
   return 0;
 }
 
+// the GELU-backward data gradient dX = (dy W) GELU'(aux) (bf16, unsplit, whole 8-column runs), with
+// or without the activation side output g.aux_out: the IMP 9 epilogue, persistent where that pays
+void launch_dx_gelu(const GemmArgs& g, hipStream_t st) {
+  if (pp_ok_gelu_bwd(g) && launch_pp<false, 9>(g, st)) return;
+  launch_v2<true, false, __bf16, true, 9>(g, 1, st);
+}
+
 // implicit-conv GEMMs (bf16 operands, N % 8 == 0): IMP 1 = A implicit (forward,
 // data gradient: A K-major, B = packed weights [N][K]); IMP 2 = B implicit (weight
 // gradient: A = dy stored [K][M], fp32 split-K slabs)
 template <int IMP, typename TC>
 void launch_conv(const GemmArgs& g, int splits, hipStream_t st) {
-  const int v = gemm_variant(g.M, g.N, 0) == 2 ? 2 : 3;
-  const int bm = variant_bm(v);
   constexpr bool AK = IMP == 1 || IMP == 10, BK = AK;
   if constexpr (IMP == 1) {
-    if (g.N <= 64 && v == 2) {   // narrow output (the stem's 48-channel data gradient): 64-column tiles
+    // narrow output (the stem's 48-channel data gradient): 64-column tiles
+    if (g.N <= 64 && gemm_variant(g.M, g.N) == 256) {
       const dim3 grid(((g.N + 63) / 64) * ((g.M + 255) / 256) * splits);
       hipLaunchKernelGGL((gemm_bf16_v2<AK, BK, TC, true, 256, IMP, 64>), grid, dim3(512), 0, st, g);
       return;
     }
   }
-  dim3 grid(((g.N + 127) / 128) * ((g.M + bm - 1) / bm) * splits);
-  if (v == 2) hipLaunchKernelGGL((gemm_bf16_v2<AK, BK, TC, true, 256, IMP>), grid, dim3(512), 0, st, g);
-  else hipLaunchKernelGGL((gemm_bf16_v2<AK, BK, TC, true, 128, IMP>), grid, dim3(256), 0, st, g);
+  launch_v2<AK, BK, TC, true, IMP>(g, splits, st);
 }
 
 GemmArgs conv_args(int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
@@ -2206,24 +2102,11 @@ extern "C" int sm_conv3x3_wgrad(const void* dy, const void* x, float* dw, int ac
   const int N = 9 * Cin;
   GemmArgs g = conv_args(Cout, N, (int)P, dy, Cout, x, N, dw, N, H, W, Cin, 0);
   g.beta = accumulate ? 1.f : 0.f;
-  int splits = choose_splits(Cout, N, (int)P, true);
-  if (splits > 1 && (ws == nullptr || ws_bytes < (int64_t)splits * Cout * N * 4)) splits = 1;
-  if (splits > 1) {
-    int chunk = (int)((P + splits - 1) / splits);
-    chunk = (chunk + BKT - 1) / BKT * BKT;
-    splits = (int)((P + chunk - 1) / chunk);
-    g.k_chunk = chunk;
-    g.partial = (float*)ws;
-  }
+  const int splits = plan_splitk(g, choose_splits(Cout, N, (int)P, true), BKT, ws, ws_bytes);
   launch_conv<2, float>(g, splits, st);
   SM_CHECK_LAUNCH();
-  if (splits > 1) {
-    const int64_t total = (int64_t)Cout * N;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(splitk_reduce_kernel<float>, dim3(blocks), dim3(256), 0, st, g, splits);
-    SM_CHECK_LAUNCH();
-  }
+  launch_splitk_reduce<float>(g, splits, st);
+  SM_CHECK_LAUNCH();
   return 0;
 }
 
@@ -2271,44 +2154,20 @@ static int gemm_run(int ab_dtype, int c_dtype, int a_layout, int b_layout, int M
   g.colsum = colsum;
   int splits = choose_splits(M, N, K, ab_dtype == SM_BF16);
   if (ab_dtype == SM_BF16 && c_dtype == SM_F32 && a_layout == 1 && b_layout == 1) splits = dw384_splits(M, N, splits);
-  if (splits > 1 && (workspace == nullptr || ws_bytes < (int64_t)splits * M * N * 4)) splits = 1;
-  const int bk = ab_dtype == SM_BF16 ? BKT : FBK;
-  if (K <= 0) {  // empty reduction: C = beta*C + bias (epilogue only)
-    g.k_begin = 0; g.k_chunk = 0;
-  } else if (splits > 1) {
-    int chunk = (K + splits - 1) / splits;
-    chunk = (chunk + bk - 1) / bk * bk;
-    splits = (K + chunk - 1) / chunk;
-    g.k_begin = 0; g.k_chunk = chunk; g.partial = (float*)workspace;
-  } else {
-    g.k_begin = 0; g.k_chunk = K;
-  }
-  int rc;
+  splits = plan_splitk(g, splits, ab_dtype == SM_BF16 ? BKT : FBK, workspace, ws_bytes);
+  int rc = 0;
   if ((epi & 4) && ab_dtype == SM_BF16 && c_dtype == SM_BF16 && a_layout == 0 && b_layout == 1 && splits == 1 &&
-      !((N & 7) || (ldc & 7)) && K > 0) {   // the GELU-backward dX GEMM: IMP 9 epilogue
-    const int v = gemm_variant(M, N, K);
-    const int tiles = ((N + 127) / 128) * ((M + variant_bm(v) - 1) / variant_bm(v));
-    if (v == 2 && pp_ok_gelu_bwd(g) && launch_pp<false, 9>(g, stream)) {
-      SM_CHECK_LAUNCH();
-      return 0;
-    }
-    if (v == 2) hipLaunchKernelGGL((gemm_bf16_v2<true, false, __bf16, true, 256, 9>), dim3(tiles), dim3(512), 0, stream, g);
-    else hipLaunchKernelGGL((gemm_bf16_v2<true, false, __bf16, true, 128, 9>), dim3(tiles), dim3(256), 0, stream, g);
+      !((N & 7) || (ldc & 7)) && K > 0) {
+    launch_dx_gelu(g, stream);
     SM_CHECK_LAUNCH();
-    rc = 0;
   } else if (a_layout == 0 && b_layout == 0) rc = launch_layout<true, true>(ab_dtype, c_dtype, g, splits, stream);
   else if (a_layout == 0 && b_layout == 1) rc = launch_layout<true, false>(ab_dtype, c_dtype, g, splits, stream);
   else if (a_layout == 1 && b_layout == 0) rc = launch_layout<false, true>(ab_dtype, c_dtype, g, splits, stream);
   else rc = launch_layout<false, false>(ab_dtype, c_dtype, g, splits, stream);
   if (rc) return rc;
-  if (splits > 1) {
-    const int64_t total = (int64_t)M * N;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    if (c_dtype == SM_BF16) hipLaunchKernelGGL(splitk_reduce_kernel<__bf16>, dim3(blocks), dim3(256), 0, stream, g, splits);
-    else hipLaunchKernelGGL(splitk_reduce_kernel<float>, dim3(blocks), dim3(256), 0, stream, g, splits);
-    SM_CHECK_LAUNCH();
-  }
+  if (c_dtype == SM_BF16) launch_splitk_reduce<__bf16>(g, splits, stream);
+  else launch_splitk_reduce<float>(g, splits, stream);
+  SM_CHECK_LAUNCH();
   if (colsum) {
     colred(colsum, K > 0 ? splits : 0, M, nullptr, colsum_out, 1, stream);
     SM_CHECK_LAUNCH();
@@ -2330,14 +2189,7 @@ extern "C" int sm_linear_dx_gelu(int M, int N, int K, const void* dy, const void
   g.M = M; g.N = K; g.K = N; g.A = dy; g.lda = N; g.B = w; g.ldb = K; g.C = dx; g.ldc = K;
   g.alpha = 1.f; g.beta = 0.f; g.epi = 4; g.aux = const_cast<void*>(pre); g.aux_out = h;
   g.drop_p = drop_p; g.seed = seed; g.rows_per_group = 1; g.k_begin = 0; g.k_chunk = N;
-  const int v = gemm_variant(g.M, g.N, g.K);
-  const int tiles = ((g.N + 127) / 128) * ((g.M + variant_bm(v) - 1) / variant_bm(v));
-  if (v == 2 && pp_ok_gelu_bwd(g) && launch_pp<false, 9>(g, stream)) {
-    SM_CHECK_LAUNCH();
-    return 0;
-  }
-  if (v == 2) hipLaunchKernelGGL((gemm_bf16_v2<true, false, __bf16, true, 256, 9>), dim3(tiles), dim3(512), 0, stream, g);
-  else hipLaunchKernelGGL((gemm_bf16_v2<true, false, __bf16, true, 128, 9>), dim3(tiles), dim3(256), 0, stream, g);
+  launch_dx_gelu(g, stream);
   SM_CHECK_LAUNCH();
   return 0;
 }
@@ -2359,10 +2211,7 @@ extern "C" int sm_linear_dx2(int M, int N, int K1, int K2, const void* a1, int64
   g.A2 = a2; g.lda2 = lda2; g.k1 = K1;
   g.bias = bias; g.alpha = 1.f; g.beta = residual ? 1.f : 0.f; g.R = residual;
   g.rows_per_group = 1; g.k_begin = 0; g.k_chunk = g.K;
-  const int v = gemm_variant(M, N, g.K) == 2 ? 2 : 3;
-  const int tiles = ((N + 127) / 128) * ((M + variant_bm(v) - 1) / variant_bm(v));
-  if (v == 2) hipLaunchKernelGGL((gemm_bf16_v2<true, false, __bf16, true, 256, 14>), dim3(tiles), dim3(512), 0, stream, g);
-  else hipLaunchKernelGGL((gemm_bf16_v2<true, false, __bf16, true, 128, 14>), dim3(tiles), dim3(256), 0, stream, g);
+  launch_v2<true, false, __bf16, true, 14>(g, 1, stream);
   SM_CHECK_LAUNCH();
   return 0;
 }
@@ -2386,8 +2235,8 @@ extern "C" int sm_colsum(int dtype, int64_t M, int C, const void* x, float* out,
 namespace {
 // Output rows x columns the bf16 v2 kernel computes for an M x N product (tile quantisation).
 int64_t tiled_area(int M, int N) {
-  const int bm = variant_bm(gemm_variant(M, N, 0));
-  return (int64_t)((M + bm - 1) / bm) * bm * ((N + 127) / 128) * 128;
+  const int bm = gemm_variant(M, N);
+  return v2_tiles(M, N, bm) * bm * 128;
 }
 // dW = dy^T x computed transposed (dW^T = x^T dy: M = nin, N = nout) when that tiles the
 // output with less waste and still splits K (the transposed store lives in the split-K
@@ -2399,7 +2248,7 @@ bool dw_transposed(int rows, int nout, int nin) {
   // the 384 x 128 weight-gradient tile divides [384 k][128 n] outputs as they are (fc2's [384][1536]):
   // no transposed store, and the bias gradient stays fused (no separate column-sum pass): -3.9 %
   // (profiles/r06zjk_dw384_ab.txt, r06zm)
-  if (g_tune[TUNE_DW384] && g_tune[TUNE_DW384_NOTR] && nout % DW3_BM == 0 && nin % DW3_BN == 0) return false;
+  if (g_tune[TUNE_DW384_NOTR] && dw384_ok(nout, nin)) return false;
   return tiled_area(nin, nout) == (int64_t)nin * nout && tiled_area(nout, nin) * 10 > (int64_t)nout * nin * 11 &&
          choose_splits(nin, nout, rows, true) > 1;
 }
@@ -2423,8 +2272,6 @@ extern "C" int sm_linear_dw_bias_gelu(int rows, int nout, int nin, const void* d
   if (nout <= 0 || nin <= 0 || rows <= 0) return 0;
   if (ws_bytes < sm_linear_dw_bias_workspace_bytes(rows, nout, nin)) return -4;
   if (nout % 8 || nin % 8 || (((uintptr_t)dy | (uintptr_t)pre) & 15)) return -2;
-  const int v = gemm_variant(nout, nin, rows);
-  if (v == 1) return -2;
   const int s = choose_splits(nout, nin, rows, true);
   const int64_t gbytes = s > 1 ? (int64_t)s * nout * nin * 4 : 0;
   float* colsum = (float*)(((uintptr_t)ws + gbytes + 15) & ~(uintptr_t)15);
@@ -2432,37 +2279,16 @@ extern "C" int sm_linear_dw_bias_gelu(int rows, int nout, int nin, const void* d
   g.M = nout; g.N = nin; g.K = rows; g.A = dy; g.lda = nout; g.B = pre; g.ldb = nin; g.C = dW; g.ldc = nin;
   g.alpha = 1.f; g.beta = accumulate ? 1.f : 0.f; g.rows_per_group = 1; g.colsum = colsum;
   g.xb_p = drop_p; g.xb_seed = seed;
-  int splits = s;
-  if (splits > 1) {
-    int chunk = (rows + splits - 1) / splits;
-    chunk = (chunk + BKT - 1) / BKT * BKT;
-    splits = (rows + chunk - 1) / chunk;
-    g.k_begin = 0; g.k_chunk = chunk; g.partial = (float*)ws;
-  } else {
-    g.k_begin = 0; g.k_chunk = rows;
-  }
-  const int bm = variant_bm(v);
-  const dim3 grid(((nin + 127) / 128) * ((nout + bm - 1) / bm) * splits);
-  if (v == 2) hipLaunchKernelGGL((gemm_bf16_v2<false, false, float, true, 256, 5>), grid, dim3(512), 0, stream, g);
-  else hipLaunchKernelGGL((gemm_bf16_v2<false, false, float, true, 128, 5>), grid, dim3(256), 0, stream, g);
+  const int splits = plan_splitk(g, s, BKT, ws, ws_bytes);
+  launch_v2<false, false, float, true, 5>(g, splits, stream);
   SM_CHECK_LAUNCH();
-  if (splits > 1) {
-    const int64_t total = (int64_t)nout * nin;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(splitk_reduce_kernel<float>, dim3(blocks), dim3(256), 0, stream, g, splits);
-    SM_CHECK_LAUNCH();
-  }
+  launch_splitk_reduce<float>(g, splits, stream);
+  SM_CHECK_LAUNCH();
   colred(colsum, splits, nout, nullptr, db, 1, stream);
   SM_CHECK_LAUNCH();
   return 0;
 }
 
-// The MBConv projection's weight gradient over the SE output (tiny_vit.py:29-34, 53):
-// dW[nout][nin] (+)= dy^T h3 with h3[r][c] = bf16(bf16(GELU(a2[r][c] sc[c] + sh[c])) *
-// gate[r / hw][c]) formed in the B-operand loads (IMP 7): se_scale's h3 pass (read a2,
-// write h3, read it back) disappears.  a2 [rows][nin] bf16, dy [rows][nout] bf16;
-// rows = frames * hw with hw % 64 == 0 (each 64-row K-step inside one frame).
 // The MBConv projection's forward over the SE output (tiny_vit.py:29-34, 53): y[rows][nout]
 // (bf16) = h3 W^T with h3[r][c] = bf16(bf16(act(a2[r][c])) * gate[r / hw][c]) formed in the
 // A-operand loads (IMP 6): se_apply's h3 pass (read a2, write h3, read it back) is gone;
@@ -2480,7 +2306,7 @@ extern "C" int sm_linear_se(int rows, int nout, int nin, const void* a2, const v
   g.alpha = 1.f; g.beta = 0.f; g.rows_per_group = 1; g.k_begin = 0; g.k_chunk = nin;
   g.xb_act = ChanAffine{act_mean, act_rstd, act_w, act_b, act_gelu};
   g.xb_gate = gate; g.xb_hw = hw;
-  const dim3 grid(((nout + 127) / 128) * ((rows + 127) / 128));
+  const dim3 grid((unsigned)v2_tiles(rows, nout, 128));   // BM = 128 whatever M: a tile inside one frame
   hipLaunchKernelGGL((gemm_bf16_v2<true, true, __bf16, true, 128, 6>), grid, dim3(256), 0, stream, g);
   SM_CHECK_LAUNCH();
   return 0;
@@ -2524,36 +2350,41 @@ extern "C" int sm_bn_stats_from_partials(const float* part, int64_t nrows, int C
                                          float momentum, float eps, int updates, void* ws, int64_t ws_bytes,
                                          hipStream_t st);
 
+namespace {
+// How the *_bn_stats entry points end.  The GEMM's epilogue (g.stat_part = ws) has left the
+// per-slab partials [ceil(M / 64)][2][N] at the start of a sm_linear_bn_stats_workspace_bytes(M, N)
+// workspace; they are summed in row chunks into the area behind them, which
+// sm_bn_stats_from_partials finishes (its fp64 scratch comes last).
+int bn_stats_finish(void* ws, int64_t M, int N, float* mean, float* rstd, float* run_mean, float* run_var,
+                    int64_t* num_batches_tracked, float momentum, float eps, int updates, hipStream_t st) {
+  const int64_t nparts = (M + 63) / 64;
+  float* part = (float*)ws;
+  float* part2 = part + nparts * 2 * N;
+  void* fin = (void*)(((uintptr_t)(part2 + (int64_t)LBS_CHUNKS * 2 * N) + 15) & ~(uintptr_t)15);
+  const int64_t chunk = (nparts + LBS_CHUNKS - 1) / LBS_CHUNKS;
+  const int nch = (int)((nparts + chunk - 1) / chunk);
+  hipLaunchKernelGGL(rowchunk_sum_kernel, dim3((2 * N + 31) / 32, nch), dim3(256), 0, st, part, nparts, 2 * N, chunk,
+                     part2);
+  SM_CHECK_LAUNCH();
+  return sm_bn_stats_from_partials(part2, nch, N, M, mean, rstd, run_mean, run_var, num_batches_tracked, momentum,
+                                   eps, updates, fin, 2 * (int64_t)N * 8, st);
+}
+}  // namespace
+
 extern "C" int sm_linear_bn_stats(int M, int N, int K, const void* x, const void* w, void* y, float* mean, float* rstd,
                                   float* run_mean, float* run_var, int64_t* num_batches_tracked, float momentum,
                                   float eps, int updates, void* ws, int64_t ws_bytes, hipStream_t stream) {
   if (M <= 0 || N <= 0) return -2;
   if (K <= 0 || K % 8 || N % 8 || (((uintptr_t)x | (uintptr_t)w | (uintptr_t)y) & 15)) return -2;
   if (ws_bytes < sm_linear_bn_stats_workspace_bytes(M, N)) return -4;
-  const int64_t nparts = (M + 63) / 64;
-  float* part = (float*)ws;
-  float* part2 = part + nparts * 2 * N;
-  void* fin = (void*)(((uintptr_t)(part2 + (int64_t)LBS_CHUNKS * 2 * N) + 15) & ~(uintptr_t)15);
   GemmArgs g{};
   g.M = M; g.N = N; g.K = K; g.A = x; g.lda = K; g.B = w; g.ldb = K; g.C = y; g.ldc = N;
   g.alpha = 1.f; g.beta = 0.f; g.rows_per_group = 1; g.k_begin = 0; g.k_chunk = K;
-  g.stat_part = part;
-  const int tiles_n = (N + 127) / 128;
-  if (gemm_variant(M, N, K) == 2 && pp_ok(g) && launch_pp<true, 8>(g, stream)) {
-  } else if (gemm_variant(M, N, K) == 2)
-    hipLaunchKernelGGL((gemm_bf16_v2<true, true, __bf16, true, 256, 8>), dim3(tiles_n * ((M + 255) / 256)), dim3(512),
-                       0, stream, g);
-  else
-    hipLaunchKernelGGL((gemm_bf16_v2<true, true, __bf16, true, 128, 8>), dim3(tiles_n * ((M + 127) / 128)), dim3(256),
-                       0, stream, g);
+  g.stat_part = (float*)ws;
+  if (!(pp_ok(g) && launch_pp<true, 8>(g, stream))) launch_v2<true, true, __bf16, true, 8>(g, 1, stream);
   SM_CHECK_LAUNCH();
-  const int64_t chunk = (nparts + LBS_CHUNKS - 1) / LBS_CHUNKS;
-  const int nch = (int)((nparts + chunk - 1) / chunk);
-  hipLaunchKernelGGL(rowchunk_sum_kernel, dim3((2 * N + 31) / 32, nch), dim3(256), 0, stream, part, nparts, 2 * N,
-                     chunk, part2);
-  SM_CHECK_LAUNCH();
-  return sm_bn_stats_from_partials(part2, nch, N, M, mean, rstd, run_mean, run_var, num_batches_tracked, momentum,
-                                   eps, updates, fin, 2 * (int64_t)N * 8, stream);
+  return bn_stats_finish(ws, M, N, mean, rstd, run_mean, run_var, num_batches_tracked, momentum, eps, updates,
+                         stream);
 }
 
 // stem conv2 forward + the output's train-mode BatchNorm statistics from the GEMM epilogue (as
@@ -2565,21 +2396,12 @@ extern "C" int sm_conv3x3_fwd_bn_stats(const void* x, const void* wpack, void* y
   const int64_t P = (int64_t)F * H * W;
   if (!conv_shape_ok(P, H, W, Cin, Cout, x, wpack, y)) return -2;
   if (ws_bytes < sm_linear_bn_stats_workspace_bytes((int)P, Cout)) return -4;
-  const int64_t nparts = (P + 63) / 64;
-  float* part = (float*)ws;
-  float* part2 = part + nparts * 2 * Cout;
-  void* fin = (void*)(((uintptr_t)(part2 + (int64_t)LBS_CHUNKS * 2 * Cout) + 15) & ~(uintptr_t)15);
   GemmArgs g = conv_args((int)P, Cout, 9 * Cin, x, Cin, wpack, 9 * Cin, y, Cout, H, W, Cin, 0);
-  g.stat_part = part;
+  g.stat_part = (float*)ws;
   launch_conv<10, __bf16>(g, 1, st);
   SM_CHECK_LAUNCH();
-  const int64_t chunk = (nparts + LBS_CHUNKS - 1) / LBS_CHUNKS;
-  const int nch = (int)((nparts + chunk - 1) / chunk);
-  hipLaunchKernelGGL(rowchunk_sum_kernel, dim3((2 * Cout + 31) / 32, nch), dim3(256), 0, st, part, nparts, 2 * Cout,
-                     chunk, part2);
-  SM_CHECK_LAUNCH();
-  return sm_bn_stats_from_partials(part2, nch, Cout, P, mean, rstd, run_mean, run_var, num_batches_tracked, momentum,
-                                   eps, updates, fin, 2 * (int64_t)Cout * 8, st);
+  return bn_stats_finish(ws, P, Cout, mean, rstd, run_mean, run_var, num_batches_tracked, momentum, eps, updates,
+                         st);
 }
 
 // The stem's BN2 folded into stage 0's first MBConv (tiny_vit.py:62-72 -> :43): the expand
@@ -2599,21 +2421,11 @@ static int linear_bnin_launch(int M, int N, int K, const void* a, const float* m
   g.alpha = 1.f; g.beta = 0.f; g.rows_per_group = 1; g.k_begin = 0; g.k_chunk = K;
   g.xb_act = ChanAffine{mean, rstd, bw, bb, 0};
   g.stat_part = stat_part;
-  const int tiles_n = (N + 127) / 128;
-  if (gemm_variant(M, N, K) == 2 && pp_ok(g)) {   // persistent form (K <= 128: the stage-0 expand)
-    if (stat_part ? launch_pp<true, 11>(g, stream) : launch_pp<true, 12>(g, stream)) {
-      SM_CHECK_LAUNCH();
-      return 0;
-    }
-  }
-  if (gemm_variant(M, N, K) == 2) {
-    const dim3 grid(tiles_n * ((M + 255) / 256));
-    if (stat_part) hipLaunchKernelGGL((gemm_bf16_v2<true, true, __bf16, true, 256, 11>), grid, dim3(512), 0, stream, g);
-    else hipLaunchKernelGGL((gemm_bf16_v2<true, true, __bf16, true, 256, 12>), grid, dim3(512), 0, stream, g);
+  // persistent form (K <= 128: the stage-0 expand) where it pays
+  if (stat_part) {
+    if (!(pp_ok(g) && launch_pp<true, 11>(g, stream))) launch_v2<true, true, __bf16, true, 11>(g, 1, stream);
   } else {
-    const dim3 grid(tiles_n * ((M + 127) / 128));
-    if (stat_part) hipLaunchKernelGGL((gemm_bf16_v2<true, true, __bf16, true, 128, 11>), grid, dim3(256), 0, stream, g);
-    else hipLaunchKernelGGL((gemm_bf16_v2<true, true, __bf16, true, 128, 12>), grid, dim3(256), 0, stream, g);
+    if (!(pp_ok(g) && launch_pp<true, 12>(g, stream))) launch_v2<true, true, __bf16, true, 12>(g, 1, stream);
   }
   SM_CHECK_LAUNCH();
   return 0;
@@ -2631,19 +2443,10 @@ extern "C" int sm_linear_bnin_bn_stats(int M, int N, int K, const void* a, const
                                        hipStream_t stream) {
   if (M <= 0 || N <= 0) return -2;
   if (ws_bytes < sm_linear_bn_stats_workspace_bytes(M, N)) return -4;
-  const int64_t nparts = (M + 63) / 64;
-  float* part = (float*)ws;
-  float* part2 = part + nparts * 2 * N;
-  void* fin = (void*)(((uintptr_t)(part2 + (int64_t)LBS_CHUNKS * 2 * N) + 15) & ~(uintptr_t)15);
-  const int rc = linear_bnin_launch(M, N, K, a, a_mean, a_rstd, a_w, a_b, w, y, part, stream);
+  const int rc = linear_bnin_launch(M, N, K, a, a_mean, a_rstd, a_w, a_b, w, y, (float*)ws, stream);
   if (rc) return rc;
-  const int64_t chunk = (nparts + LBS_CHUNKS - 1) / LBS_CHUNKS;
-  const int nch = (int)((nparts + chunk - 1) / chunk);
-  hipLaunchKernelGGL(rowchunk_sum_kernel, dim3((2 * N + 31) / 32, nch), dim3(256), 0, stream, part, nparts, 2 * N,
-                     chunk, part2);
-  SM_CHECK_LAUNCH();
-  return sm_bn_stats_from_partials(part2, nch, N, M, mean, rstd, run_mean, run_var, num_batches_tracked, momentum,
-                                   eps, updates, fin, 2 * (int64_t)N * 8, stream);
+  return bn_stats_finish(ws, M, N, mean, rstd, run_mean, run_var, num_batches_tracked, momentum, eps, updates,
+                         stream);
 }
 
 extern "C" int64_t sm_linear_dw_se_workspace_bytes(int rows, int nout, int nin) {
@@ -2651,6 +2454,11 @@ extern "C" int64_t sm_linear_dw_se_workspace_bytes(int rows, int nout, int nin) 
   return s > 1 ? (int64_t)s * nout * nin * 4 : 16;
 }
 
+// The MBConv projection's weight gradient over the SE output (tiny_vit.py:29-34, 53):
+// dW[nout][nin] (+)= dy^T h3 with h3[r][c] = bf16(bf16(GELU(a2[r][c] sc[c] + sh[c])) *
+// gate[r / hw][c]) formed in the B-operand loads (IMP 7): se_scale's h3 pass (read a2,
+// write h3, read it back) disappears.  a2 [rows][nin] bf16, dy [rows][nout] bf16;
+// rows = frames * hw with hw % 64 == 0 (each 64-row K-step inside one frame).
 extern "C" int sm_linear_dw_se(int rows, int nout, int nin, const void* dy, const void* a2, const float* act_mean,
                                const float* act_rstd, const float* act_w, const float* act_b, int act_gelu,
                                const float* gate, int hw, float* dW, int accumulate, void* ws, int64_t ws_bytes,
@@ -2660,34 +2468,17 @@ extern "C" int sm_linear_dw_se(int rows, int nout, int nin, const void* dy, cons
   if (nout % 8 || nin % 8 || (((uintptr_t)dy | (uintptr_t)a2) & 15)) return -2;
   if (gate != nullptr && (hw <= 0 || hw % BKT || rows % hw)) return -2;   // no gate: any rows (x = BN(a2))
   if (act_mean == nullptr) return -2;
-  const int v = gemm_variant(nout, nin, rows);
-  if (v == 1) return -2;
   GemmArgs g{};
   g.M = nout; g.N = nin; g.K = rows; g.A = dy; g.lda = nout; g.B = a2; g.ldb = nin; g.C = dW; g.ldc = nin;
   g.alpha = 1.f; g.beta = accumulate ? 1.f : 0.f; g.rows_per_group = 1;
   g.xb_act = ChanAffine{act_mean, act_rstd, act_w, act_b, act_gelu};
   g.xb_gate = gate; g.xb_hw = gate ? hw : 1;
-  int splits = choose_splits(nout, nin, rows, true);
-  if (splits > 1) {
-    int chunk = (rows + splits - 1) / splits;
-    chunk = (chunk + BKT - 1) / BKT * BKT;     // K-steps never straddle a frame (hw % BKT == 0)
-    splits = (rows + chunk - 1) / chunk;
-    g.k_begin = 0; g.k_chunk = chunk; g.partial = (float*)ws;
-  } else {
-    g.k_begin = 0; g.k_chunk = rows;
-  }
-  const int bm = variant_bm(v);
-  const dim3 grid(((nin + 127) / 128) * ((nout + bm - 1) / bm) * splits);
-  if (v == 2) hipLaunchKernelGGL((gemm_bf16_v2<false, false, float, true, 256, 7>), grid, dim3(512), 0, stream, g);
-  else hipLaunchKernelGGL((gemm_bf16_v2<false, false, float, true, 128, 7>), grid, dim3(256), 0, stream, g);
+  // split chunks are multiples of BKT: K-steps never straddle a frame (hw % BKT == 0)
+  const int splits = plan_splitk(g, choose_splits(nout, nin, rows, true), BKT, ws, ws_bytes);
+  launch_v2<false, false, float, true, 7>(g, splits, stream);
   SM_CHECK_LAUNCH();
-  if (splits > 1) {
-    const int64_t total = (int64_t)nout * nin;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(splitk_reduce_kernel<float>, dim3(blocks), dim3(256), 0, stream, g, splits);
-    SM_CHECK_LAUNCH();
-  }
+  launch_splitk_reduce<float>(g, splits, stream);
+  SM_CHECK_LAUNCH();
   return 0;
 }
 
@@ -2695,7 +2486,7 @@ extern "C" int sm_linear_dw_bias(int rows, int nout, int nin, const void* dy, co
                                  int accumulate, void* ws, int64_t ws_bytes, hipStream_t stream) {
   if (nout <= 0 || nin <= 0) return 0;
   if (ws_bytes < sm_linear_dw_bias_workspace_bytes(rows, nout, nin)) return -4;
-  if (gemm_variant(nout, nin, rows) == 1 || nout % 8 || nin % 8) return -2;   // the row sums live in the v2 kernel
+  if (nout % 8 || nin % 8) return -2;
   if (dw_transposed(rows, nout, nin)) {
     // dW^T[nin][nout] = x^T dy (split-K slabs), reduced into dW[nout][nin] through the
     // transposed store; db = column sums of dy by the colsum kernel (the fused row sums
@@ -2705,16 +2496,10 @@ extern "C" int sm_linear_dw_bias(int rows, int nout, int nin, const void* dy, co
     GemmArgs g{};
     g.M = nin; g.N = nout; g.K = rows; g.A = x; g.lda = nin; g.B = dy; g.ldb = nout; g.C = dW; g.ldc = nin;
     g.alpha = 1.f; g.beta = accumulate ? 1.f : 0.f; g.rows_per_group = 1; g.ctrans = 1;
-    int chunk = (rows + s - 1) / s;
-    chunk = (chunk + BKT - 1) / BKT * BKT;
-    const int splits = (rows + chunk - 1) / chunk;
-    g.k_begin = 0; g.k_chunk = chunk; g.partial = (float*)ws;
+    const int splits = plan_splitk(g, s, BKT, ws, ws_bytes);
     launch_bf16<false, false, float, true>(g, splits, stream);
     SM_CHECK_LAUNCH();
-    const int64_t total = (int64_t)nout * nin;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(splitk_reduce_kernel<float>, dim3(blocks), dim3(256), 0, stream, g, splits);
+    launch_splitk_reduce<float>(g, splits, stream);
     SM_CHECK_LAUNCH();
     void* cws = (void*)(((uintptr_t)ws + gbytes + 255) & ~(uintptr_t)255);
     return sm_colsum(SM_BF16, rows, nout, dy, db, 1, cws, sm_colsum_workspace_bytes(rows, nout), stream);
