@@ -307,22 +307,18 @@ int sm_dwconv_fused_bwd(int F, int H, int W, int C, int stride, const void* dy, 
                         const float* in_mean, const float* in_rstd, const float* in_w, const float* in_b,
                         int in_gelu, const float* w, void* dx, float* dw, void* ws, int64_t ws_bytes,
                         hipStream_t st);
-// Stride-1 depthwise conv + BatchNorm(+GELU) backward that never stores the depthwise
+// Depthwise conv (stride 1 or 2) + BatchNorm + GELU backward that never stores the depthwise
 // data gradient (one pass over dy forming dw, dz = g GELU' and the BN sums, one
 // streaming pass dz -> dx, dx doubling as the dz buffer): dx = dL/dx for y = dwconv3x3(GELU(BN(x))), dw += dL/dw,
 // dgamma / dbeta += the BatchNorm's (MBConv conv1 -> act -> conv2, tiny_vit.py:36-56;
-// replaces sm_dwconv_fused_bwd + sm_bn_bwd on that path).
+// replaces sm_dwconv_fused_bwd + sm_bn_bwd on that path).  F, H, W, C are the input's, dy is
+// [F][(H-1)/stride+1][(W-1)/stride+1][C] (stride 2: the MBConv opening stages 1-3).  The GELU
+// is built into the kernels: bn_gelu == 0 is refused (-2), here and in sm_dwconv_bn_bwd_dz.
 int64_t sm_dwconv_bn_bwd_workspace_bytes(int F, int H, int W, int C);
-int sm_dwconv_bn_bwd(int F, int H, int W, int C, const void* dy, const void* x, const float* bn_mean,
+int sm_dwconv_bn_bwd(int stride, int F, int H, int W, int C, const void* dy, const void* x, const float* bn_mean,
                      const float* bn_rstd, const float* bn_w, const float* bn_b, int bn_gelu, const float* w,
                      void* dx, float* dw, float* dgamma, float* dbeta, void* ws, int64_t ws_bytes,
                      hipStream_t st);
-/* Stride-2 form (the MBConv opening stages 1-3): F, H, W, C are the input's, dy is
- * [F][(H-1)/2+1][(W-1)/2+1][C]; same outputs and workspace (sm_dwconv_bn_bwd_workspace_bytes). */
-int sm_dwconv_s2_bn_bwd(int F, int H, int W, int C, const void* dy, const void* x, const float* bn_mean,
-                        const float* bn_rstd, const float* bn_w, const float* bn_b, int bn_gelu, const float* w,
-                        void* dx, float* dw, float* dgamma, float* dbeta, void* ws, int64_t ws_bytes,
-                        hipStream_t st);
 /* The first pass alone (stride 1 or 2; same shapes, outputs and workspace): dz = g GELU'(BN(x))
  * stays in dz [F][H][W][C], coef [2][C] = mean(dz), mean(dz xhat); the BatchNorm's dx map
  * dx = bn_w rstd (dz - coef[0] - xhat coef[1]) is left to the consumer (sm_mbconv_fold_prep). */

@@ -715,6 +715,8 @@ struct DwRing {
   static constexpr int TY = TY_;
   static constexpr int NR = (TY - 1) * S + 3;
   static constexpr int NEW = TY * S;              // rows entering the ring per band
+  // first of the NEW rows that enter with `band` (> 0; band 0 is stage_first's)
+  static SM_DEV int first_new(int band) { return band * NEW + 2 - S; }
   const __bf16* x;
   int64_t f;
   int H, W, C, cbase, c8, pitch;
@@ -779,7 +781,50 @@ struct DwRing {
     commit<REMAT>(lds, af, -1 + first, NR - first);
     zero_borders(lds);
   }
+  // entry of `band` (after stage_first): its prefetched rows into the ring, then the next
+  // band's new rows in flight (registers) while the caller computes this one
+  template <bool REMAT = false>
+  SM_DEV void enter(char* lds, const Affine8& af, int band, int nbands) {
+    if (band > 0) {
+      __syncthreads();                                  // band-1 finished reading the slots we overwrite
+      commit<REMAT>(lds, af, first_new(band), NEW);
+    }
+    __syncthreads();
+    if (band + 1 < nbands) load<REMAT>(first_new(band + 1), NEW);
+  }
 };
+
+// Dynamic LDS of the fused depthwise kernels, read by the kernels and by the host that
+// sizes it: the ring [NR][W + 2][32] bf16, PAD zero bytes behind its last row, the taps
+// [9][32] fp32 and (BN) the BatchNorm constants [4][32] fp32.  Once the ring is dead the
+// block reductions reuse RED bytes from the start.  W: the ring's row width.
+template <class R, int PAD, bool BN, int RED>
+struct DwLds {
+  int pad, taps, bn, total;
+  __host__ __device__ constexpr DwLds(int W)
+      : pad(R::NR * (W + 2) * 64), taps(pad + PAD), bn(taps + 9 * DWF_CB * 4),
+        total(bn + (BN ? 4 * DWF_CB * 4 : 0) < RED ? RED : bn + (BN ? 4 * DWF_CB * 4 : 0)) {}
+};
+template <int S>
+using DwfLds = DwLds<DwRing<S>, 0, false, 256 * 16 * 4>;   // dwf_fwd_kernel ([256][16]), dwf_wgrad_kernel ([256][8])
+
+// wl[tap][ch] = w[cbase + ch][tap] (rot: [8 - tap], the taps rotated 180 degrees)
+SM_DEV void dw_stage_taps(float* wl, const float* w, int cbase, bool rot) {
+  for (int i = threadIdx.x; i < 9 * DWF_CB; i += 256) {
+    const int tap = i / DWF_CB, ch = i % DWF_CB;
+    wl[i] = w[(int64_t)(cbase + ch) * 9 + (rot ? 8 - tap : tap)];
+  }
+}
+
+// The block reductions of the fused depthwise kernels: every thread has written K per-channel
+// sums of its channel group (t % G of the block's 32 channels) to red[t][K]; the sum of
+// column col over the 256 / G threads of group g, in thread order.
+template <int G, int K>
+SM_DEV float dw_group_sum(const float* red, int g, int col) {
+  float a = 0.f;
+  for (int k = 0; k < 256 / G; ++k) a += red[(k * G + g) * K + col];
+  return a;
+}
 
 // Block -> (32-channel slice, frame) of the fused depthwise kernels.  1-D grid with
 // the bijective XCD remap (as the attention and GEMM kernels): the C/32 slices of a
@@ -824,11 +869,8 @@ __global__ __launch_bounds__(256, 2) void dwf_fwd_kernel(const __bf16* x, ChanAf
   af.init(act, cbase);
   // taps in LDS after the ring ([9][32] fp32), re-read per row of taps: keeps the
   // 72 weights out of the register file (occupancy); 6 ds_read_b128 per item row
-  float* wl = (float*)(lds + R::NR * ring.pitch);
-  for (int i = t; i < 9 * DWF_CB; i += 256) {
-    const int tap = i / DWF_CB, ch = i % DWF_CB;
-    wl[i] = w[(int64_t)(cs * DWF_CB + ch) * 9 + tap];
-  }
+  float* wl = (float*)(lds + DwfLds<S>(W).taps);
+  dw_stage_taps(wl, w, cs * DWF_CB, false);
   float s8[8], q8[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) { s8[j] = 0.f; q8[j] = 0.f; }
@@ -837,13 +879,8 @@ __global__ __launch_bounds__(256, 2) void dwf_fwd_kernel(const __bf16* x, ChanAf
   const int nbands = (Ho + TY - 1) / TY;
   ring.stage_first(lds, af);
   for (int band = 0; band < nbands; ++band) {
+    ring.enter(lds, af, band, nbands);
     const int yo0 = band * TY;
-    if (band > 0) {
-      __syncthreads();                                  // band-1 finished reading the slots we overwrite
-      ring.commit(lds, af, (yo0 * S - 1) + (3 - S), R::NEW);
-    }
-    __syncthreads();
-    if (band + 1 < nbands) ring.load(((yo0 + TY) * S - 1) + (3 - S), R::NEW);   // next band, in flight
     for (int it = t; it < items; it += 256) {
       const int q = it >> 2;
       const int ry = q / nstrip, strip = q - ry * nstrip;
@@ -902,10 +939,7 @@ __global__ __launch_bounds__(256, 2) void dwf_fwd_kernel(const __bf16* x, ChanAf
   __syncthreads();
   if (t < 2 * DWF_CB) {
     const int ch = t & (DWF_CB - 1), which = t / DWF_CB;
-    const int g = ch >> 3, j = ch & 7;
-    float a = 0.f;
-    for (int k = 0; k < 64; ++k) a += red[(k * 4 + g) * 16 + which * 8 + j];
-    part[(f * 2 + which) * C + cs * DWF_CB + ch] = a;
+    part[(f * 2 + which) * C + cs * DWF_CB + ch] = dw_group_sum<4, 16>(red, ch >> 3, which * 8 + (ch & 7));
   }
 }
 
@@ -941,13 +975,8 @@ __global__ __launch_bounds__(256, 2) void dwf_wgrad_kernel(const __bf16* dy, con
   const int nbands = (Ho + TY - 1) / TY;
   ring.stage_first(lds, af);
   for (int band = 0; band < nbands; ++band) {
+    ring.enter(lds, af, band, nbands);
     const int yo0 = band * TY;
-    if (band > 0) {
-      __syncthreads();
-      ring.commit(lds, af, (yo0 * S - 1) + (3 - S), R::NEW);
-    }
-    __syncthreads();
-    if (band + 1 < nbands) ring.load(((yo0 + TY) * S - 1) + (3 - S), R::NEW);
     for (int it = t; it < items; it += 256) {
       const int q = it >> 2;
       const int ry = q / nstrip, strip = q - ry * nstrip;
@@ -982,19 +1011,14 @@ __global__ __launch_bounds__(256, 2) void dwf_wgrad_kernel(const __bf16* dy, con
       }
     }
   }
-  __syncthreads();
-  float* red = (float*)lds;   // [256][8] per tap
+  __syncthreads();            // ring dead: reuse for the reductions, [256][8] per tap
+  float* red = (float*)lds;
 #pragma unroll
   for (int tap = 0; tap < 9; ++tap) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) red[t * 8 + j] = acc[tap][j];
     __syncthreads();
-    if (t < DWF_CB) {
-      const int g = t >> 3, j = t & 7;
-      float a = 0.f;
-      for (int k = 0; k < 64; ++k) a += red[(k * 4 + g) * 8 + j];
-      part[(f * C + cs * DWF_CB + t) * 9 + tap] = a;
-    }
+    if (t < DWF_CB) part[(f * C + cs * DWF_CB + t) * 9 + tap] = dw_group_sum<4, 8>(red, t >> 3, t & 7);
     __syncthreads();
   }
 }
@@ -1020,12 +1044,113 @@ __global__ __launch_bounds__(256, 2) void dwf_wgrad_kernel(const __bf16* dy, con
 constexpr int DWB_PX = 7, DWB_PAD = 8 * 64;
 typedef __attribute__((ext_vector_type(2))) unsigned int v2u32_t;
 
+// LDS of dwb_kernel / dwb2_kernel (reductions: [256][4] floats)
+template <class R, int PAD>
+using DwbLds = DwLds<R, PAD, true, 256 * 4 * 4>;
+
+// ---- what the two dwb kernels share.  A thread's item is PX pixels x 4 channels (c4 = t & 7);
+// RAG = a ragged last strip per row.
+
+// zero pad behind the ring, taps (rot: rotated 180 degrees) and per-channel BN constants
+// [4][32]: scale, shift (u = x sc + sh), mean, rstd, at the offsets of L
+template <class L>
+SM_DEV void dwb_stage(char* lds, const L& l, const float* w, bool rot, const ChanAffine& bn, int cbase) {
+  const int t = threadIdx.x;
+  for (int i = t; i < (l.taps - l.pad) / 16; i += 256) *(uint4*)(lds + l.pad + 16 * i) = make_uint4(0, 0, 0, 0);
+  dw_stage_taps((float*)(lds + l.taps), w, cbase, rot);
+  float* cl = (float*)(lds + l.bn);
+  if (t < DWF_CB) {
+    const int c = cbase + t;
+    const float r = bn.rstd[c], scv = r * bn.w[c];
+    cl[t] = scv;
+    cl[DWF_CB + t] = bn_shift(bn.b[c], bn.mean[c], scv);
+    cl[2 * DWF_CB + t] = bn.mean[c];
+    cl[3 * DWF_CB + t] = r;
+  }
+}
+
+// frame f of p [F][H][W][C] as a buffer view.  Wave-uniform descriptors: a per-row
+// descriptor built from each thread's item is divergent, and every buffer access
+// through it became a waterfall loop of up to 8 passes
+SM_DEV auto dwb_frame_view(const __bf16* p, int64_t f, int H, int W, int C) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)(p + f * H * W * C), (short)0, H * W * C * 2, 0x00020000);
+}
+
+// byte offset of pixel p of an item (from b) in the frame view; in = false (past W): out of
+// range (loads read 0, stores are dropped)
+SM_DEV uint32_t dwb_px_off(uint32_t b, int p, int C, bool in) { return in ? b + (uint32_t)(p * C * 2) : 0x80000000u; }
+
+// one GELU evaluation for a pair of elements: h = GELU(u) before its rounding to the stored
+// precision, gg = GELU'(u), u = x sc + sh
+struct DwbAct {
+  f32x2 h, gg;
+};
+SM_DEV DwbAct dwb_act(f32x2 x, f32x2 sc, f32x2 sh) {   // packed pairs (gelu_phi_pair_t)
+  const f32x2 u = vfma(x, sc, sh);
+  f32x2 pdf;
+  const f32x2 cdf = gelu_phi_pair_t<f32x2>(u, &pdf);
+  DwbAct r;
+  {
+#pragma clang fp contract(off)
+    r.h = u * cdf;
+  }
+  r.gg = vfma(u, pdf, cdf);
+  return r;
+}
+
+// dz = g GELU'(u) stored (bf16) through the view zr, and its BatchNorm-backward sums
+// (cl4: the BN constants at the thread's channels)
+template <int PX, class Rsrc>
+SM_DEV void dwb_store_dz(const float* cl4, const float (&g)[PX][4], const float (&gg)[PX][4],
+                         const bf16x4 (&xs)[PX], const uint32_t (&offp)[PX], Rsrc zr, float (&sdz)[4],
+                         float (&sdzx)[4]) {
+  float mu[4], rs[4];
+  load4(cl4 + 2 * DWF_CB, mu);
+  load4(cl4 + 3 * DWF_CB, rs);
+#pragma unroll
+  for (int p = 0; p < PX; ++p) {
+    float d[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      d[j] = (float)(__bf16)(g[p][j] * gg[p][j]);   // the stored dz: the sums see what dx will
+      sdz[j] += d[j];
+      sdzx[j] = fmaf(d[j], ((float)xs[p][j] - mu[j]) * rs[j], sdzx[j]);
+    }
+    bf16x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = (__bf16)d[j];
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u32_t, o), zr, offp[p], 0, 0);
+  }
+}
+
+// the block's sums -> part_w [f][C][9], part_bn [f][2][C]
+SM_DEV void dwb_finish(char* lds, const float (&dwa)[9][4], const float (&sdz)[4], const float (&sdzx)[4],
+                       float* part_w, float* part_bn, int64_t f, int C, int cbase) {
+  __syncthreads();                     // ring dead: reuse for the reductions
+  float* red = (float*)lds;
+  const int t = threadIdx.x;
+  auto reduce = [&](const float* v4, float* dst, int64_t stride) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) red[t * 4 + j] = v4[j];
+    __syncthreads();
+    if (t < DWF_CB) dst[(int64_t)t * stride] = dw_group_sum<8, 4>(red, t >> 2, t & 3);
+    __syncthreads();
+  };
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap) reduce(dwa[tap], part_w + (f * C + cbase) * 9 + tap, 9);
+  reduce(sdz, part_bn + (f * 2 + 0) * C + cbase, 1);
+  reduce(sdzx, part_bn + (f * 2 + 1) * C + cbase, 1);
+}
+
 // RAG: W % PX != 0 (a ragged last strip per row; the stride-2 form drops the per-pixel
-// range selects when every strip is whole, as at all TinyViT widths)
+// range selects when every strip is whole, as at all TinyViT widths).  GELU is always on
+// (no MBConv is without it); the parameter only keeps the instance names that profiles/
+// and DESIGN.md refer to.
 template <bool GELU, bool RAG>
 __global__ __launch_bounds__(256, 2) void dwb_kernel(const __bf16* dy, const __bf16* x, ChanAffine bn,
                                                      const float* w, __bf16* dz, float* part_w, float* part_bn,
                                                      int H, int W, int C, int remap) {
+  static_assert(GELU, "the identity-activation form is gone");
   using R = DwRing<1>;
   constexpr int TY = R::TY;
   constexpr int PX = DWB_PX;
@@ -1039,25 +1164,10 @@ __global__ __launch_bounds__(256, 2) void dwb_kernel(const __bf16* dy, const __b
   raw.init(ChanAffine{nullptr, nullptr, nullptr, nullptr, 0}, 0);
   const int c4 = t & 7;
   const int c0 = cs * DWF_CB + c4 * 4;
-  char* pad = lds + R::NR * ring.pitch;
-  for (int i = t; i < DWB_PAD / 16; i += 256) *(uint4*)(pad + 16 * i) = make_uint4(0, 0, 0, 0);
-  // rotated taps: wl[tap][ch] = w[ch][8 - tap]
-  float* wl = (float*)(pad + DWB_PAD);
-  for (int i = t; i < 9 * DWF_CB; i += 256) {
-    const int tap = i / DWF_CB, ch = i % DWF_CB;
-    wl[i] = w[(int64_t)(cs * DWF_CB + ch) * 9 + 8 - tap];
-  }
-  // per-channel BN constants [4][32]: scale, shift (u = x sc + sh), mean, rstd
-  float* cl = wl + 9 * DWF_CB;
-  if (t < DWF_CB) {
-    const int c = cs * DWF_CB + t;
-    const float r = bn.rstd[c], scv = r * bn.w[c];
-    cl[t] = scv;
-    cl[DWF_CB + t] = bn_shift(bn.b[c], bn.mean[c], scv);
-    cl[2 * DWF_CB + t] = bn.mean[c];
-    cl[3 * DWF_CB + t] = r;
-  }
-  float dwa[9][4], sdz[4], sdzx[4];
+  const DwbLds<R, DWB_PAD> L(W);
+  dwb_stage(lds, L, w, true, bn, cs * DWF_CB);
+  const float *wl = (const float*)(lds + L.taps), *cl = (const float*)(lds + L.bn);
+  float dwa[9][4], sdz[4], sdzx[4];   // dw[tap], sum dz, sum dz xhat of the thread's 4 channels
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     sdz[j] = sdzx[j] = 0.f;
@@ -1066,33 +1176,23 @@ __global__ __launch_bounds__(256, 2) void dwb_kernel(const __bf16* dy, const __b
   }
   const int nstrip = (W + PX - 1) / PX;
   const int items = TY * nstrip;
+  const auto xr = dwb_frame_view(x, f, H, W, C);
+  const auto zr = dwb_frame_view(dz, f, H, W, C);
   const int nbands = (H + TY - 1) / TY;
-  // frame-level views of x and dz (wave-uniform descriptors: a per-row descriptor built from
-  // each thread's item is divergent, and every buffer access through it became a waterfall
-  // loop of up to 8 passes)
-  const auto xr = __builtin_amdgcn_make_buffer_rsrc((void*)(x + f * H * W * C), (short)0, H * W * C * 2, 0x00020000);
-  const auto zr = __builtin_amdgcn_make_buffer_rsrc((void*)(dz + f * H * W * C), (short)0, H * W * C * 2, 0x00020000);
   ring.stage_first<true>(lds, raw);
   for (int band = 0; band < nbands; ++band) {
+    ring.enter<true>(lds, raw, band, nbands);
     const int y0 = band * TY;
-    if (band > 0) {
-      __syncthreads();
-      ring.commit<true>(lds, raw, y0 + 1, R::NEW);
-    }
-    __syncthreads();
-    if (band + 1 < nbands) ring.load<true>(y0 + TY + 1, R::NEW);
 #pragma unroll 1
     for (int it = t >> 3; it < items; it += 32) {
       const int ry = it / nstrip, strip = it - ry * nstrip;
       const int yi = y0 + ry;
       if (yi >= H) continue;
       const int xi0 = strip * PX;
-      // this pixel row of x and dz as buffer views: pixels past W read 0 / drop stores
-      // pixels past W: out-of-range offset (loads read 0, stores are dropped)
-      const uint32_t off0 = (uint32_t)((yi * W + xi0) * C + c0) * 2u;
       uint32_t offp[PX];
+      const uint32_t off0 = (uint32_t)((yi * W + xi0) * C + c0) * 2u;
 #pragma unroll
-      for (int p = 0; p < PX; ++p) offp[p] = (!RAG || xi0 + p < W) ? off0 + (uint32_t)(p * C * 2) : 0x80000000u;
+      for (int p = 0; p < PX; ++p) offp[p] = dwb_px_off(off0, p, C, !RAG || xi0 + p < W);
       float h[PX][4], gg[PX][4], g[PX][4];
       bf16x4 xs[PX];                     // x itself (xhat is formed after the tap loop)
       {
@@ -1106,21 +1206,13 @@ __global__ __launch_bounds__(256, 2) void dwb_kernel(const __bf16* dy, const __b
         for (int p = 0; p < PX; ++p) {
           const bool ok = !RAG || xi0 + p < W;
 #pragma unroll
-          for (int j = 0; j < 4; j += 2) {   // packed pairs (gelu_phi_pair_t)
-            const f32x2 u = vfma(f32x2{(float)xs[p][j], (float)xs[p][j + 1]}, f32x2{sc[j], sc[j + 1]},
-                                 f32x2{sh[j], sh[j + 1]});
-            f32x2 cdf = f32x2{1.f, 1.f}, pdf = f32x2{0.f, 0.f};
-            if (GELU) cdf = gelu_phi_pair_t<f32x2>(u, &pdf);
-            f32x2 hv = u;
-            if (GELU) {
-#pragma clang fp contract(off)
-              hv = u * cdf;
-            }
-            const f32x2 gv = vfma(u, pdf, cdf);
-            h[p][j] = ok ? (float)(__bf16)hv.x : 0.f;
-            h[p][j + 1] = ok ? (float)(__bf16)hv.y : 0.f;
-            gg[p][j] = ok ? gv.x : 0.f;
-            gg[p][j + 1] = ok ? gv.y : 0.f;
+          for (int j = 0; j < 4; j += 2) {
+            const DwbAct a = dwb_act(f32x2{(float)xs[p][j], (float)xs[p][j + 1]}, f32x2{sc[j], sc[j + 1]},
+                                     f32x2{sh[j], sh[j + 1]});
+            h[p][j] = ok ? (float)(__bf16)a.h.x : 0.f;
+            h[p][j + 1] = ok ? (float)(__bf16)a.h.y : 0.f;
+            gg[p][j] = ok ? a.gg.x : 0.f;
+            gg[p][j + 1] = ok ? a.gg.y : 0.f;
             g[p][j] = g[p][j + 1] = 0.f;
           }
           __builtin_amdgcn_sched_barrier(0);   // bound the interleaved GELU chains (VGPR budget)
@@ -1149,43 +1241,10 @@ __global__ __launch_bounds__(256, 2) void dwb_kernel(const __bf16* dy, const __b
         }
         __builtin_amdgcn_sched_barrier(0);   // one tap row's reads in flight at a time (VGPR budget)
       }
-      float mu[4], rs[4];
-      load4(cl + 2 * DWF_CB + c4 * 4, mu);
-      load4(cl + 3 * DWF_CB + c4 * 4, rs);
-#pragma unroll
-      for (int p = 0; p < PX; ++p) {
-        float d[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          d[j] = (float)(__bf16)(g[p][j] * gg[p][j]);   // the stored dz: the sums see what dx will
-          sdz[j] += d[j];
-          sdzx[j] = fmaf(d[j], ((float)xs[p][j] - mu[j]) * rs[j], sdzx[j]);
-        }
-        bf16x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (__bf16)d[j];
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u32_t, o), zr, offp[p], 0, 0);
-      }
+      dwb_store_dz(cl + c4 * 4, g, gg, xs, offp, zr, sdz, sdzx);
     }
   }
-  __syncthreads();                     // ring dead: reuse for the reductions
-  float* red = (float*)lds;            // [256][4]
-  auto reduce = [&](const float* v4, float* dst, int64_t stride) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) red[t * 4 + j] = v4[j];
-    __syncthreads();
-    if (t < DWF_CB) {
-      const int cc = t >> 2, j = t & 3;
-      float s = 0.f;
-      for (int k = 0; k < 32; ++k) s += red[(k * 8 + cc) * 4 + j];
-      dst[(int64_t)t * stride] = s;
-    }
-    __syncthreads();
-  };
-#pragma unroll
-  for (int tap = 0; tap < 9; ++tap) reduce(dwa[tap], part_w + (f * C + cs * DWF_CB) * 9 + tap, 9);
-  reduce(sdz, part_bn + (f * 2 + 0) * C + cs * DWF_CB, 1);
-  reduce(sdzx, part_bn + (f * 2 + 1) * C + cs * DWF_CB, 1);
+  dwb_finish(lds, dwa, sdz, sdzx, part_w, part_bn, f, C, cs * DWF_CB);
 }
 
 // Stride-2 form of dwb_kernel (the MBConv that opens stages 1-3: tiny_vit.py:46 with
@@ -1205,9 +1264,12 @@ template <bool GELU, bool RAG>
 __global__ __launch_bounds__(256, 2) void dwb2_kernel(const __bf16* dy, const __bf16* x, ChanAffine bn,
                                                       const float* w, __bf16* dz, float* part_w, float* part_bn,
                                                       int H, int W, int C, int Ho, int Wo, int remap) {
+  static_assert(GELU, "the identity-activation form is gone");
   using R = DwRing<1, DWB2_TYO>;
   constexpr int TYI = 2 * DWB2_TYO;      // input rows per band
   constexpr int PX = DWB2_PX;
+  // DWB2_PAD: a ragged last strip's pixels past W read up to two columns past the last ring
+  // row: zero pad, so those values (which only meet h = GELU' = 0) are never NaN bit patterns
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const DwfBlock blk(C / DWF_CB, remap);
   const int cs = blk.cs;
@@ -1218,25 +1280,10 @@ __global__ __launch_bounds__(256, 2) void dwb2_kernel(const __bf16* dy, const __
   raw.init(ChanAffine{nullptr, nullptr, nullptr, nullptr, 0}, 0);
   const int c4 = t & 7;
   const int c0 = cs * DWF_CB + c4 * 4;
-  // a ragged last strip's pixels past W read up to two columns past the last ring row:
-  // zero pad, so those values (which only meet h = GELU' = 0) are never NaN bit patterns
-  char* pad = lds + R::NR * ring.pitch;
-  if (t < DWB2_PAD / 16) *(uint4*)(pad + 16 * t) = make_uint4(0, 0, 0, 0);
-  float* wl = (float*)(pad + DWB2_PAD);              // taps wl[tap][ch] = w[ch][tap]
-  for (int i = t; i < 9 * DWF_CB; i += 256) {
-    const int tap = i / DWF_CB, ch = i % DWF_CB;
-    wl[i] = w[(int64_t)(cs * DWF_CB + ch) * 9 + tap];
-  }
-  float* cl = wl + 9 * DWF_CB;                      // BN constants [4][32]: scale, shift, mean, rstd
-  if (t < DWF_CB) {
-    const int c = cs * DWF_CB + t;
-    const float r = bn.rstd[c], scv = r * bn.w[c];
-    cl[t] = scv;
-    cl[DWF_CB + t] = bn_shift(bn.b[c], bn.mean[c], scv);
-    cl[2 * DWF_CB + t] = bn.mean[c];
-    cl[3 * DWF_CB + t] = r;
-  }
-  float dwa[9][4], sdz[4], sdzx[4];
+  const DwbLds<R, DWB2_PAD> L(Wo);
+  dwb_stage(lds, L, w, false, bn, cs * DWF_CB);
+  const float *wl = (const float*)(lds + L.taps), *cl = (const float*)(lds + L.bn);
+  float dwa[9][4], sdz[4], sdzx[4];   // dw[tap], sum dz, sum dz xhat of the thread's 4 channels
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     sdz[j] = sdzx[j] = 0.f;
@@ -1246,9 +1293,8 @@ __global__ __launch_bounds__(256, 2) void dwb2_kernel(const __bf16* dy, const __
   const int nstrip = (W + PX - 1) / PX;
   const int items = TYI * nstrip;
   const int nbands = (H + TYI - 1) / TYI;
-  // frame-level views of x and dz (wave-uniform descriptors; see dwb_kernel)
-  const auto xr = __builtin_amdgcn_make_buffer_rsrc((void*)(x + f * H * W * C), (short)0, H * W * C * 2, 0x00020000);
-  const auto zr = __builtin_amdgcn_make_buffer_rsrc((void*)(dz + f * H * W * C), (short)0, H * W * C * 2, 0x00020000);
+  const auto xr = dwb_frame_view(x, f, H, W, C);
+  const auto zr = dwb_frame_view(dz, f, H, W, C);
   // item offsets; the thread's NEXT item's x is loaded while the current one computes
   // (-2 % here, profiles/r04g_dwb_prefetch_ab.txt; the stride-1 kernel, already at 235
   // VGPRs, spilled with it and lost 3 %)
@@ -1257,7 +1303,7 @@ __global__ __launch_bounds__(256, 2) void dwb2_kernel(const __bf16* dy, const __
     const int xi_ = strip * PX;
     const uint32_t b = (uint32_t)(((band_ * TYI + ry) * W + xi_) * C + c0) * 2u;
 #pragma unroll
-    for (int p = 0; p < PX; ++p) o[p] = (!RAG || xi_ + p < W) ? b + (uint32_t)(p * C * 2) : 0x80000000u;
+    for (int p = 0; p < PX; ++p) o[p] = dwb_px_off(b, p, C, !RAG || xi_ + p < W);
   };
   auto xload = [&](const uint32_t (&o)[PX], bf16x4 (&xv)[PX]) {
 #pragma unroll
@@ -1272,13 +1318,8 @@ __global__ __launch_bounds__(256, 2) void dwb2_kernel(const __bf16* dy, const __
   }
   ring.stage_first<true>(lds, raw);
   for (int band = 0; band < nbands; ++band) {
-    const int y0 = band * TYI, yo0 = band * DWB2_TYO;
-    if (band > 0) {
-      __syncthreads();
-      ring.commit<true>(lds, raw, yo0 + 1, R::NEW);
-    }
-    __syncthreads();
-    if (band + 1 < nbands) ring.load<true>(yo0 + DWB2_TYO + 1, R::NEW);
+    ring.enter<true>(lds, raw, band, nbands);
+    const int y0 = band * TYI;
 #pragma unroll 1
     for (int it = t >> 3; it < items; it += 32) {
       const int ry = it / nstrip, strip = it - ry * nstrip;
@@ -1311,21 +1352,13 @@ __global__ __launch_bounds__(256, 2) void dwb2_kernel(const __bf16* dy, const __
         for (int p = 0; p < PX; ++p) {
           const bool ok = !RAG || xi0 + p < W;
 #pragma unroll
-          for (int j = 0; j < 4; j += 2) {   // packed pairs (gelu_phi_pair_t)
-            const f32x2 u = vfma(f32x2{(float)xs[p][j], (float)xs[p][j + 1]}, f32x2{sc[j], sc[j + 1]},
-                                 f32x2{sh[j], sh[j + 1]});
-            f32x2 cdf = f32x2{1.f, 1.f}, pdf = f32x2{0.f, 0.f};
-            if (GELU) cdf = gelu_phi_pair_t<f32x2>(u, &pdf);
-            f32x2 hv = u;
-            if (GELU) {
-#pragma clang fp contract(off)
-              hv = u * cdf;
-            }
-            const f32x2 gv = vfma(u, pdf, cdf);
-            h[p][j] = ok ? (float)(__bf16)hv.x : 0.f;
-            h[p][j + 1] = ok ? (float)(__bf16)hv.y : 0.f;
-            gg[p][j] = ok ? gv.x : 0.f;
-            gg[p][j + 1] = ok ? gv.y : 0.f;
+          for (int j = 0; j < 4; j += 2) {
+            const DwbAct a = dwb_act(f32x2{(float)xs[p][j], (float)xs[p][j + 1]}, f32x2{sc[j], sc[j + 1]},
+                                     f32x2{sh[j], sh[j + 1]});
+            h[p][j] = ok ? (float)(__bf16)a.h.x : 0.f;
+            h[p][j + 1] = ok ? (float)(__bf16)a.h.y : 0.f;
+            gg[p][j] = ok ? a.gg.x : 0.f;
+            gg[p][j + 1] = ok ? a.gg.y : 0.f;
             g[p][j] = g[p][j + 1] = 0.f;
           }
           __builtin_amdgcn_sched_barrier(0);   // bound the interleaved GELU chains (VGPR budget)
@@ -1361,43 +1394,10 @@ __global__ __launch_bounds__(256, 2) void dwb2_kernel(const __bf16* dy, const __
       } else {
         tap_row(1, yi >> 1);
       }
-      float mu[4], rs[4];
-      load4(cl + 2 * DWF_CB + c4 * 4, mu);
-      load4(cl + 3 * DWF_CB + c4 * 4, rs);
-#pragma unroll
-      for (int p = 0; p < PX; ++p) {
-        float d[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          d[j] = (float)(__bf16)(g[p][j] * gg[p][j]);   // the stored dz: the sums see what dx will
-          sdz[j] += d[j];
-          sdzx[j] = fmaf(d[j], ((float)xs[p][j] - mu[j]) * rs[j], sdzx[j]);
-        }
-        bf16x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (__bf16)d[j];
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u32_t, o), zr, offp[p], 0, 0);
-      }
+      dwb_store_dz(cl + c4 * 4, g, gg, xs, offp, zr, sdz, sdzx);
     }
   }
-  __syncthreads();                     // ring dead: reuse for the reductions
-  float* red = (float*)lds;            // [256][4]
-  auto reduce = [&](const float* v4, float* dst, int64_t stride) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) red[t * 4 + j] = v4[j];
-    __syncthreads();
-    if (t < DWF_CB) {
-      const int cc = t >> 2, j = t & 3;
-      float s = 0.f;
-      for (int k = 0; k < 32; ++k) s += red[(k * 8 + cc) * 4 + j];
-      dst[(int64_t)t * stride] = s;
-    }
-    __syncthreads();
-  };
-#pragma unroll
-  for (int tap = 0; tap < 9; ++tap) reduce(dwa[tap], part_w + (f * C + cs * DWF_CB) * 9 + tap, 9);
-  reduce(sdz, part_bn + (f * 2 + 0) * C + cs * DWF_CB, 1);
-  reduce(sdzx, part_bn + (f * 2 + 1) * C + cs * DWF_CB, 1);
+  dwb_finish(lds, dwa, sdz, sdzx, part_w, part_bn, f, C, cs * DWF_CB);
 }
 
 // dx = w rstd (dz - coef[0] - xhat coef[1]) in place over dz; thread = fixed 8-channel
@@ -1536,6 +1536,13 @@ struct SeCols {
     c0 = (threadIdx.x % nch) * 8;
     r = threadIdx.x / nch;
   }
+  // red [256][8] holds every thread's 8 sums: channel c's sum over the rpp threads of its
+  // column, in thread order
+  SM_DEV float block_sum(const float* red, int c) const {
+    float a = 0.f;
+    for (int rr = 0; rr < rpp; ++rr) a += red[(rr * nch + c / 8) * 8 + c % 8];
+    return a;
+  }
 };
 
 // part[f][k][c] = sum over split k of h  (h = act(x))      or of dy * h when dy
@@ -1571,11 +1578,7 @@ __global__ __launch_bounds__(256) void se_reduce_kernel(const T* x, const T* dy,
 #pragma unroll
   for (int j = 0; j < 8; ++j) red[threadIdx.x * 8 + j] = s[j];
   __syncthreads();
-  for (int c = threadIdx.x; c < C; c += 256) {
-    float a = 0.f;
-    for (int rr = 0; rr < cm.rpp; ++rr) a += red[(rr * cm.nch + c / 8) * 8 + c % 8];
-    part[(f * nsplit + k) * C + c] = a;
-  }
+  for (int c = threadIdx.x; c < C; c += 256) part[(f * nsplit + k) * C + c] = cm.block_sum(red, c);
 }
 
 // per frame: p = sum_k part / HW; z1 = W1 p; h1 = relu(z1); z2 = W2 h1; s = sigmoid(z2)
@@ -1758,8 +1761,7 @@ __global__ __launch_bounds__(256) void se_bn_reduce_kernel(const T* dy, const T*
     for (int j = 0; j < 8; ++j) red[threadIdx.x * 8 + j] = acc[q][j];
     __syncthreads();
     for (int c = threadIdx.x; c < C; c += 256) {
-      float a = 0.f;
-      for (int rr = 0; rr < cm.rpp; ++rr) a += red[(rr * cm.nch + c / 8) * 8 + c % 8];
+      const float a = cm.block_sum(red, c);
       if (q == 0) part[(f * nsplit + k) * C + c] = a;
       else part2[((f * nsplit + k) * 4 + (q - 1)) * C + c] = a;
     }
@@ -1847,14 +1849,20 @@ __global__ __launch_bounds__(256) void se_bn_dx_kernel(const T* dy, const T* x, 
     else { typedef __bf16 T; __VA_ARGS__; }                    \
   } while (0)
 
-// every host-side Ho / Wo computation divides by the stride: only 1 and 2 exist
+// conv_out divides by the stride: only 1 and 2 exist, checked once per entry point
 static bool bad_stride(int s) { return s != 1 && s != 2; }
+
+// output size of a 3x3 / pad 1 convolution
+struct OutDims {
+  int Ho, Wo;
+};
+static OutDims conv_out(int H, int W, int stride) { return {(H + 2 - 3) / stride + 1, (W + 2 - 3) / stride + 1}; }
 
 extern "C" int sm_stem_im2col(int out_dtype, const float* clip, int B, int T, int H, int W, int64_t sB, int64_t sC,
                               int64_t sT, int64_t sH, int64_t sW, int stride, void* col, hipStream_t st) {
   ClipView v{clip, B, T, H, W, sB, sC, sT, sH, sW};
   if (bad_stride(stride)) return -2;
-  const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
+  const auto [Ho, Wo] = conv_out(H, W, stride);
   const int64_t P = (int64_t)B * T * Ho * Wo;
   if (P <= 0) return 0;
   DISPATCH1(out_dtype, hipLaunchKernelGGL(stem_im2col_kernel<T>, dim3(ew_blocks(P)), dim3(256), 0, st, v, Ho, Wo,
@@ -1877,7 +1885,7 @@ extern "C" int sm_stem_conv1_bn_stats(const float* clip, int B, int T, int H, in
                                       float momentum, float eps, int updates, void* ws, int64_t ws_bytes,
                                       hipStream_t st) {
   ClipView v{clip, B, T, H, W, sB, sC, sT, sH, sW};
-  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  const auto [Ho, Wo] = conv_out(H, W, 2);
   const int64_t P = (int64_t)B * T * Ho * Wo;
   if (P <= 0) return 0;
   if (P >= (1LL << 31) - 64 || (int64_t)3 * sC >= (1LL << 31)) return -2;
@@ -1933,7 +1941,7 @@ extern "C" int sm_im2col3(int dtype, const void* x, int F, int H, int W, int C, 
                           hipStream_t st) {
   if (C % 8) return -2;
   if (bad_stride(stride)) return -2;
-  const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
+  const auto [Ho, Wo] = conv_out(H, W, stride);
   const int64_t total = (int64_t)F * Ho * Wo * 9 * (C / 8);
   if (total <= 0) return 0;
   DISPATCH1(dtype, hipLaunchKernelGGL(im2col3_kernel<T>, dim3(ew_blocks(total)), dim3(256), 0, st, (const T*)x, F,
@@ -1946,7 +1954,7 @@ extern "C" int sm_col2im3(int dtype, const void* dcol, int F, int H, int W, int 
                           hipStream_t st) {
   if (C % 8) return -2;
   if (bad_stride(stride)) return -2;
-  const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
+  const auto [Ho, Wo] = conv_out(H, W, stride);
   const int64_t total = (int64_t)F * H * W * (C / 8);
   if (total <= 0) return 0;
   DISPATCH1(dtype, hipLaunchKernelGGL(col2im3_kernel<T>, dim3(ew_blocks(total)), dim3(256), 0, st, (const T*)dcol,
@@ -1978,34 +1986,55 @@ extern "C" int sm_dwconv_fwd(int dtype, const void* x, const float* w, void* y, 
                              int stride, hipStream_t st) {
   if (C % 8) return -2;
   if (bad_stride(stride)) return -2;
-  const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
+  const auto [Ho, Wo] = conv_out(H, W, stride);
   const int64_t total = (int64_t)F * Ho * ((Wo + DW_PX - 1) / DW_PX) * (C / 8);
   if (total <= 0) return 0;
   const int nb = (int)((total + 255) / 256);
-  if (stride == 1)
-    DISPATCH1(dtype, hipLaunchKernelGGL((dw_fwd_kernel<T, 1>), dim3(nb), dim3(256), 0, st, (const T*)x, w, (T*)y, F,
-                                        H, W, C, Ho, Wo));
-  else if (stride == 2)
-    DISPATCH1(dtype, hipLaunchKernelGGL((dw_fwd_kernel<T, 2>), dim3(nb), dim3(256), 0, st, (const T*)x, w, (T*)y, F,
-                                        H, W, C, Ho, Wo));
-  else
-    return -2;
+  DISPATCH1(dtype, auto kern = stride == 1 ? dw_fwd_kernel<T, 1> : dw_fwd_kernel<T, 2>;
+            hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, st, (const T*)x, w, (T*)y, F, H, W, C, Ho, Wo));
   SM_CHECK_LAUNCH();
   return 0;
 }
 
-static size_t dwf_lds_bytes(int W, int stride) {
-  const int NR = stride == 1 ? DwRing<1>::NR : DwRing<2>::NR;
-  size_t lds = (size_t)NR * (W + 2) * 64 + 9 * DWF_CB * 4;   // ring + taps
-  return lds < 256 * 16 * 4 ? 256 * 16 * 4 : lds;   // the statistics reduction reuses it
+// the generic depthwise data gradient (stride checked by the caller)
+static void launch_dw_dgrad(int dtype, int stride, const void* dy, const float* w, void* dx, int F, int H, int W,
+                            int C, hipStream_t st) {
+  const auto [Ho, Wo] = conv_out(H, W, stride);
+  const int64_t total = (int64_t)F * H * ((W + DW_PX - 1) / DW_PX) * (C / 8);
+  const int nb = (int)((total + 255) / 256);
+  DISPATCH1(dtype, auto kern = stride == 1 ? dw_dgrad_kernel<T, 1> : dw_dgrad_kernel<T, 2>;
+            hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, st, (const T*)dy, w, (T*)dx, F, H, W, C, Ho, Wo));
 }
 
-static int dwf_remap() { return 1; }
+// ---- fused depthwise family: one launcher per kernel, (stride, flags) -> instance
+constexpr int DWF_REMAP = 1;   // the XCD remap of DwfBlock, always on
 
+static size_t dwf_lds_bytes(int W, int stride) { return stride == 1 ? DwfLds<1>(W).total : DwfLds<2>(W).total; }
+
+// the one stride check of every fused entry point, with the limits of the ring's register
+// prefetch (DwRing::load) and of dynamic LDS
 static bool dwf_shape_ok(int F, int W, int C, int stride) {
-  return C % DWF_CB == 0 && (stride == 1 || stride == 2) && F > 0 && (int64_t)F * (C / DWF_CB) < (1LL << 31) &&
+  return C % DWF_CB == 0 && !bad_stride(stride) && F > 0 && (int64_t)F * (C / DWF_CB) < (1LL << 31) &&
          DwRing<2>::NEW * W * 4 <= 256 * DWF_KV && DwRing<1>::NEW * W * 4 <= 256 * DWF_KV &&
          dwf_lds_bytes(W, stride) <= 64 * 1024;
+}
+
+// y [F][Ho][Wo][C] = dwconv3x3(act(x)), x [F][H][W][C]; part: the statistics partials or null
+static void launch_dwf_fwd(int stride, int F, int H, int W, int C, const void* x, const ChanAffine& act,
+                           const float* w, void* y, float* part, hipStream_t st) {
+  const auto [Ho, Wo] = conv_out(H, W, stride);
+  auto kern = stride == 1 ? (part ? dwf_fwd_kernel<1> : dwf_fwd_kernel<1, false>)
+                          : (part ? dwf_fwd_kernel<2> : dwf_fwd_kernel<2, false>);
+  hipLaunchKernelGGL(kern, dim3((C / DWF_CB) * F), dim3(256), dwf_lds_bytes(W, stride), st, (const __bf16*)x, act, w,
+                     (__bf16*)y, part, H, W, C, Ho, Wo, DWF_REMAP);
+}
+
+static void launch_dwf_wgrad(int stride, int F, int H, int W, int C, const void* dy, const void* x,
+                             const ChanAffine& act, float* part, hipStream_t st) {
+  const auto [Ho, Wo] = conv_out(H, W, stride);
+  auto kern = stride == 1 ? dwf_wgrad_kernel<1> : dwf_wgrad_kernel<2>;
+  hipLaunchKernelGGL(kern, dim3((C / DWF_CB) * F), dim3(256), dwf_lds_bytes(W, stride), st, (const __bf16*)dy,
+                     (const __bf16*)x, act, part, H, W, C, Ho, Wo, DWF_REMAP);
 }
 
 extern "C" int64_t sm_dwconv_fused_partial_rows(int F, int H, int stride) { return F; }
@@ -2015,24 +2044,7 @@ extern "C" int sm_dwconv_fused_fwd(int F, int H, int W, int C, int stride, const
                                    const float* w, void* y, float* part, hipStream_t st) {
   if (!dwf_shape_ok(F, W, C, stride)) return -2;
   if (((uintptr_t)w & 15) || ((uintptr_t)x & 15) || ((uintptr_t)y & 15)) return -2;
-  if (bad_stride(stride)) return -2;
-  const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
-  ChanAffine act{in_mean, in_rstd, in_w, in_b, in_gelu};
-  const dim3 grid((C / DWF_CB) * F);
-  const size_t lds = dwf_lds_bytes(W, stride);
-  const int remap = dwf_remap();
-  if (stride == 1 && part)
-    hipLaunchKernelGGL((dwf_fwd_kernel<1>), grid, dim3(256), lds, st, (const __bf16*)x, act, w, (__bf16*)y, part,
-                       H, W, C, Ho, Wo, remap);
-  else if (stride == 1)
-    hipLaunchKernelGGL((dwf_fwd_kernel<1, false>), grid, dim3(256), lds, st, (const __bf16*)x, act, w, (__bf16*)y,
-                       part, H, W, C, Ho, Wo, remap);
-  else if (part)
-    hipLaunchKernelGGL((dwf_fwd_kernel<2>), grid, dim3(256), lds, st, (const __bf16*)x, act, w, (__bf16*)y, part,
-                       H, W, C, Ho, Wo, remap);
-  else
-    hipLaunchKernelGGL((dwf_fwd_kernel<2, false>), grid, dim3(256), lds, st, (const __bf16*)x, act, w, (__bf16*)y,
-                       part, H, W, C, Ho, Wo, remap);
+  launch_dwf_fwd(stride, F, H, W, C, x, ChanAffine{in_mean, in_rstd, in_w, in_b, in_gelu}, w, y, part, st);
   SM_CHECK_LAUNCH();
   return 0;
 }
@@ -2055,53 +2067,61 @@ extern "C" int sm_dwconv_fused_bwd(int F, int H, int W, int C, int stride, const
                                    hipStream_t st) {
   if (!dwf_shape_ok(F, W, C, stride)) return -2;
   if (ws_bytes < sm_dwconv_fused_bwd_workspace_bytes(F, H, W, C, stride)) return -4;
-  if (bad_stride(stride)) return -2;
-  const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
-  const size_t lds = dwf_lds_bytes(W, stride);
   float* part = (float*)ws;
   float* wrot = (float*)(((uintptr_t)(part + (int64_t)F * C * 9) + 15) & ~(uintptr_t)15);
   if (dx) {
-    if (stride == 1) {
+    if (stride == 1) {   // dy and dx have the same size
       hipLaunchKernelGGL(dw_rotate_kernel, dim3((C * 9 + 255) / 256), dim3(256), 0, st, w, wrot, C * 9);
-      ChanAffine none{nullptr, nullptr, nullptr, nullptr, 0};
-      hipLaunchKernelGGL((dwf_fwd_kernel<1, false>), dim3((C / DWF_CB) * F), dim3(256), lds, st, (const __bf16*)dy, none,
-                         (const float*)wrot, (__bf16*)dx, (float*)nullptr, Ho, Wo, C, H, W, dwf_remap());
+      launch_dwf_fwd(1, F, H, W, C, dy, ChanAffine{nullptr, nullptr, nullptr, nullptr, 0}, wrot, dx, nullptr, st);
     } else {
-      const int64_t total = (int64_t)F * H * ((W + DW_PX - 1) / DW_PX) * (C / 8);
-      hipLaunchKernelGGL((dw_dgrad_kernel<__bf16, 2>), dim3((int)((total + 255) / 256)), dim3(256), 0, st,
-                         (const __bf16*)dy, w, (__bf16*)dx, F, H, W, C, Ho, Wo);
+      launch_dw_dgrad(SM_BF16, 2, dy, w, dx, F, H, W, C, st);
     }
   }
-  ChanAffine act{in_mean, in_rstd, in_w, in_b, in_gelu};
-  const dim3 g2((C / DWF_CB) * F);
-  if (stride == 1)
-    hipLaunchKernelGGL((dwf_wgrad_kernel<1>), g2, dim3(256), lds, st, (const __bf16*)dy, (const __bf16*)x, act, part,
-                       H, W, C, Ho, Wo, dwf_remap());
-  else
-    hipLaunchKernelGGL((dwf_wgrad_kernel<2>), g2, dim3(256), lds, st, (const __bf16*)dy, (const __bf16*)x, act, part,
-                       H, W, C, Ho, Wo, dwf_remap());
+  launch_dwf_wgrad(stride, F, H, W, C, dy, x, ChanAffine{in_mean, in_rstd, in_w, in_b, in_gelu}, part, st);
   colred(part, F, C * 9, nullptr, dw, 1, st);
   SM_CHECK_LAUNCH();
   return 0;
 }
 
-// Stride-1 depthwise + BatchNorm(+GELU) backward (dwb_kernel): dx = dL/dx for
-// y = dwconv3x3(GELU(BN(x))), dw += dL/dw, dgamma / dbeta += the BatchNorm's.
+// Depthwise + BatchNorm + GELU backward (dwb_kernel, stride 1; dwb2_kernel, stride 2): dx =
+// dL/dx for y = dwconv3x3(GELU(BN(x))), dw += dL/dw, dgamma / dbeta += the BatchNorm's.
+// F, H, W, C are the input's; dy is [F][Ho][Wo][C].
 extern "C" int64_t sm_dwconv_bn_bwd_workspace_bytes(int F, int H, int W, int C) {
   return ((int64_t)F * C * 9 + (int64_t)F * 2 * C + 2 * C) * 4 + 2 * C * 8 + 64;
+}
+
+using Dwb2Ring = DwRing<1, DWB2_TYO>;
+
+// W: the input's width (the stride-2 ring holds dy rows, Wo wide)
+static size_t dwb_lds_bytes(int W, int stride) {
+  return stride == 1 ? DwbLds<DwRing<1>, DWB_PAD>(W).total : DwbLds<Dwb2Ring, DWB2_PAD>(conv_out(W, W, 2).Wo).total;
+}
+
+// the first pass: dz into `dz`, the block partials into part_w / part_bn
+static void launch_dwb(int stride, int F, int H, int W, int C, const void* dy, const void* x, const ChanAffine& bn,
+                       const float* w, void* dz, float* part_w, float* part_bn, hipStream_t st) {
+  const dim3 grid((C / DWF_CB) * F);
+  const size_t lds = dwb_lds_bytes(W, stride);
+  if (stride == 1) {
+    // (the range-select-free form measured 256 VGPRs + 304 B of scratch: the compiler's
+    // schedule of the select-free GELU chains; it keeps the ragged form)
+    hipLaunchKernelGGL((dwb_kernel<true, true>), grid, dim3(256), lds, st, (const __bf16*)dy, (const __bf16*)x, bn, w,
+                       (__bf16*)dz, part_w, part_bn, H, W, C, DWF_REMAP);
+  } else {
+    const auto [Ho, Wo] = conv_out(H, W, 2);
+    auto kern = W % DWB2_PX ? dwb2_kernel<true, true> : dwb2_kernel<true, false>;
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const __bf16*)dy, (const __bf16*)x, bn, w, (__bf16*)dz,
+                       part_w, part_bn, H, W, C, Ho, Wo, DWF_REMAP);
+  }
 }
 
 static int dwconv_bn_bwd(int stride, int F, int H, int W, int C, const void* dy, const void* x, const float* bn_mean,
                          const float* bn_rstd, const float* bn_w, const float* bn_b, int bn_gelu, const float* w,
                          void* dx, float* dw, float* dgamma, float* dbeta, void* ws, int64_t ws_bytes,
                          hipStream_t st, float* coef_out = nullptr) {
-  if (bad_stride(stride)) return -2;
-  const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
-  size_t lds = stride == 1 ? dwf_lds_bytes(W, 1) + DWB_PAD + 4 * DWF_CB * 4
-                           : (size_t)DwRing<1, DWB2_TYO>::NR * (Wo + 2) * 64 + DWB2_PAD + 13 * DWF_CB * 4;
-  if (lds < 256 * 4 * 4) lds = 256 * 4 * 4;   // the reductions reuse it ([256][4] floats)
-  if (!dwf_shape_ok(F, W, C, stride) || !bn_mean || !dx || lds > 64 * 1024) return -2;
-  if (stride == 2 && DwRing<1, DWB2_TYO>::NEW * Wo * 4 > 256 * DWF_KV) return -2;
+  if (!dwf_shape_ok(F, W, C, stride) || !bn_mean || !dx || dwb_lds_bytes(W, stride) > 64 * 1024) return -2;
+  if (!bn_gelu) return -2;   // no MBConv is without the activation: the kernels have the GELU built in
+  if (stride == 2 && Dwb2Ring::NEW * conv_out(H, W, 2).Wo * 4 > 256 * DWF_KV) return -2;
   if (((uintptr_t)x & 15) || ((uintptr_t)dy & 15) || ((uintptr_t)dx & 15) || C / 8 > 256) return -2;
   if (ws_bytes < sm_dwconv_bn_bwd_workspace_bytes(F, H, W, C)) return -4;
   float* part_w = (float*)ws;
@@ -2111,28 +2131,7 @@ static int dwconv_bn_bwd(int stride, int F, int H, int W, int C, const void* dy,
   // coef_out: the caller keeps dz and the coefficients (sm_dwconv_bn_bwd_dz); no dx pass
   if (coef_out) coef = coef_out;
   ChanAffine bn{bn_mean, bn_rstd, bn_w, bn_b, bn_gelu};
-  const dim3 grid((C / DWF_CB) * F);
-  if (stride == 2) {
-    const bool rag = W % DWB2_PX != 0;
-    if (bn_gelu && !rag)
-      hipLaunchKernelGGL((dwb2_kernel<true, false>), grid, dim3(256), lds, st, (const __bf16*)dy, (const __bf16*)x, bn,
-                         w, (__bf16*)dx, part_w, part_bn, H, W, C, Ho, Wo, dwf_remap());
-    else if (bn_gelu)
-      hipLaunchKernelGGL((dwb2_kernel<true, true>), grid, dim3(256), lds, st, (const __bf16*)dy, (const __bf16*)x, bn,
-                         w, (__bf16*)dx, part_w, part_bn, H, W, C, Ho, Wo, dwf_remap());
-    else
-      hipLaunchKernelGGL((dwb2_kernel<false, true>), grid, dim3(256), lds, st, (const __bf16*)dy, (const __bf16*)x, bn,
-                         w, (__bf16*)dx, part_w, part_bn, H, W, C, Ho, Wo, dwf_remap());
-  } else {
-    // (the range-select-free stride-1 form measured 256 VGPRs + 304 B of scratch: the
-    // compiler's schedule of the select-free GELU chains; it keeps the ragged form)
-    if (bn_gelu)
-      hipLaunchKernelGGL((dwb_kernel<true, true>), grid, dim3(256), lds, st, (const __bf16*)dy, (const __bf16*)x, bn,
-                         w, (__bf16*)dx, part_w, part_bn, H, W, C, dwf_remap());
-    else
-      hipLaunchKernelGGL((dwb_kernel<false, true>), grid, dim3(256), lds, st, (const __bf16*)dy, (const __bf16*)x, bn,
-                         w, (__bf16*)dx, part_w, part_bn, H, W, C, dwf_remap());
-  }
+  launch_dwb(stride, F, H, W, C, dy, x, bn, w, dx, part_w, part_bn, st);
   colred(part_w, F, C * 9, nullptr, dw, 1, st);
   colred(part_bn, F, 2 * C, sums, nullptr, 0, st);
   const int64_t M = (int64_t)F * H * W;
@@ -2150,20 +2149,11 @@ static int dwconv_bn_bwd(int stride, int F, int H, int W, int C, const void* dy,
   return 0;
 }
 
-extern "C" int sm_dwconv_bn_bwd(int F, int H, int W, int C, const void* dy, const void* x, const float* bn_mean,
-                                const float* bn_rstd, const float* bn_w, const float* bn_b, int bn_gelu,
-                                const float* w, void* dx, float* dw, float* dgamma, float* dbeta, void* ws,
-                                int64_t ws_bytes, hipStream_t st) {
-  return dwconv_bn_bwd(1, F, H, W, C, dy, x, bn_mean, bn_rstd, bn_w, bn_b, bn_gelu, w, dx, dw, dgamma, dbeta, ws,
-                       ws_bytes, st);
-}
-
-// Stride-2 form (dwb2_kernel): F, H, W, C are the input's; dy is [F][Ho][Wo][C].
-extern "C" int sm_dwconv_s2_bn_bwd(int F, int H, int W, int C, const void* dy, const void* x, const float* bn_mean,
-                                   const float* bn_rstd, const float* bn_w, const float* bn_b, int bn_gelu,
-                                   const float* w, void* dx, float* dw, float* dgamma, float* dbeta, void* ws,
-                                   int64_t ws_bytes, hipStream_t st) {
-  return dwconv_bn_bwd(2, F, H, W, C, dy, x, bn_mean, bn_rstd, bn_w, bn_b, bn_gelu, w, dx, dw, dgamma, dbeta, ws,
+extern "C" int sm_dwconv_bn_bwd(int stride, int F, int H, int W, int C, const void* dy, const void* x,
+                                const float* bn_mean, const float* bn_rstd, const float* bn_w, const float* bn_b,
+                                int bn_gelu, const float* w, void* dx, float* dw, float* dgamma, float* dbeta,
+                                void* ws, int64_t ws_bytes, hipStream_t st) {
+  return dwconv_bn_bwd(stride, F, H, W, C, dy, x, bn_mean, bn_rstd, bn_w, bn_b, bn_gelu, w, dx, dw, dgamma, dbeta, ws,
                        ws_bytes, st);
 }
 
@@ -2181,7 +2171,7 @@ extern "C" int sm_dwconv_bn_bwd_dz(int stride, int F, int H, int W, int C, const
 
 extern "C" int64_t sm_dwconv_wgrad_workspace_bytes(int F, int H, int W, int C, int stride) {
   if (bad_stride(stride)) return 0;
-  const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
+  const auto [Ho, Wo] = conv_out(H, W, stride);
   const int64_t P = (int64_t)F * Ho * Wo;
   int64_t ppb = (P + 1023) / 1024;
   if (ppb < 64) ppb = 64;
@@ -2193,20 +2183,10 @@ extern "C" int sm_dwconv_bwd(int dtype, const void* dy, const void* x, const flo
                              int H, int W, int C, int stride, void* ws, int64_t ws_bytes, hipStream_t st) {
   if (C % 8 || C / 8 > 256) return -2;
   if (bad_stride(stride)) return -2;
-  const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
+  const auto [Ho, Wo] = conv_out(H, W, stride);
   const int64_t P = (int64_t)F * Ho * Wo;
   if (P <= 0) return 0;
-  if (stride != 1 && stride != 2) return -2;
-  if (dx) {
-    const int64_t total = (int64_t)F * H * ((W + DW_PX - 1) / DW_PX) * (C / 8);
-    const int nb = (int)((total + 255) / 256);
-    if (stride == 1)
-      DISPATCH1(dtype, hipLaunchKernelGGL((dw_dgrad_kernel<T, 1>), dim3(nb), dim3(256), 0, st, (const T*)dy, w,
-                                          (T*)dx, F, H, W, C, Ho, Wo));
-    else
-      DISPATCH1(dtype, hipLaunchKernelGGL((dw_dgrad_kernel<T, 2>), dim3(nb), dim3(256), 0, st, (const T*)dy, w,
-                                          (T*)dx, F, H, W, C, Ho, Wo));
-  }
+  if (dx) launch_dw_dgrad(dtype, stride, dy, w, dx, F, H, W, C, st);
   int64_t ppb = (P + 1023) / 1024;
   if (ppb < 64) ppb = 64;
   const int nb = (int)((P + ppb - 1) / ppb);

@@ -108,8 +108,7 @@ _SIGS = {
     "sm_dwconv_fused_bwd_workspace_bytes": (_c_i64, [_c_i32] * 5),
     "sm_dwconv_fused_bwd": (_c_i32, [_c_i32] * 5 + [_c_p] * 6 + [_c_i32] + [_c_p] * 4 + [_c_i64, _c_p]),
     "sm_dwconv_bn_bwd_workspace_bytes": (_c_i64, [_c_i32] * 4),
-    "sm_dwconv_bn_bwd": (_c_i32, [_c_i32] * 4 + [_c_p] * 6 + [_c_i32] + [_c_p] * 6 + [_c_i64, _c_p]),
-    "sm_dwconv_s2_bn_bwd": (_c_i32, [_c_i32] * 4 + [_c_p] * 6 + [_c_i32] + [_c_p] * 6 + [_c_i64, _c_p]),
+    "sm_dwconv_bn_bwd": (_c_i32, [_c_i32] * 5 + [_c_p] * 6 + [_c_i32] + [_c_p] * 6 + [_c_i64, _c_p]),
     "sm_dwconv_bn_bwd_dz": (_c_i32, [_c_i32] * 5 + [_c_p] * 6 + [_c_i32] + [_c_p] * 7 + [_c_i64, _c_p]),
     "sm_linear_dx2": (_c_i32, [_c_i32] * 4 + [_c_p, _c_i64, _c_p, _c_i64] + [_c_p] * 5),
     "sm_mbconv_fold_prep": (_c_i32, [_c_i32, _c_i32] + [_c_p] * 13),

@@ -689,7 +689,7 @@ def dwconv_bn_bwd(dy, x, act, w, dw_sink, dg_sink, db_sink, F, H, W, C, stride=1
     nbytes = query("sm_dwconv_bn_bwd_workspace_bytes", F, H, W, C)
     ws = _ws(nbytes, x.device)
     a = _act_args(act)
-    call("sm_dwconv_s2_bn_bwd" if stride == 2 else "sm_dwconv_bn_bwd", F, H, W, C, ptr(dy), ptr(x), a[0], a[1], a[2], a[3], a[4], ptr(w), ptr(dx),
+    call("sm_dwconv_bn_bwd", int(stride), F, H, W, C, ptr(dy), ptr(x), a[0], a[1], a[2], a[3], a[4], ptr(w), ptr(dx),
          ptr(dw_sink), ptr(dg_sink), ptr(db_sink), ptr(ws), nbytes, stream())
     return dx
 

@@ -268,7 +268,7 @@ def test_mbconv_fused_middle_vs_fp32_torch(Fr, H, C, stride):
     for got, ref, nm in ((dg0, tg0.grad, "bn0.w"), (db0, tb0.grad, "bn0.b")):
         assert rel(got, ref) < 3e-2, nm
     if True:
-        # the two-pass depthwise + BN0/GELU backward (sm_dwconv_bn_bwd / sm_dwconv_s2_bn_bwd)
+        # the two-pass depthwise + BN0/GELU backward (sm_dwconv_bn_bwd, either stride)
         # the MBConvs run: same references, and close to the unfused sequence above
         # (odd shapes of the stride-2 form: test_kernels_gpu.py::test_dwconv_bn_bwd_vs_fp32)
         dwdw_b = torch.zeros(C, 9, device=DEV)

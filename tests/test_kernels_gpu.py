@@ -1072,8 +1072,8 @@ def test_linear_se_operand(Fr, HW, N, C):
                                       (4, 7, 1536, 2), (4, 4, 768, 2), (4, 8, 384, 2),
                                       (4, 19, 64, 1), (2, 112, 96, 1)])
 def test_dwconv_bn_bwd_vs_fp32(Fr, H, C, s):
-    """The fused depthwise + BatchNorm0/GELU backward (sm_dwconv_bn_bwd, stride 1;
-    sm_dwconv_s2_bn_bwd, stride 2: odd and even sizes, ragged last strips, the zero
+    """The fused depthwise + BatchNorm0/GELU backward (sm_dwconv_bn_bwd, stride 1 and
+    stride 2: odd and even sizes, ragged last strips, the zero
     dy row past Ho) against fp32 autograd of conv2d(GELU(batch_norm(x)), groups=C) from
     the same bf16 inputs, and against the unfused sequence (depthwise backward, then
     bn_bwd)."""
@@ -1102,6 +1102,29 @@ def test_dwconv_bn_bwd_vs_fp32(Fr, H, C, s):
     assert rel_err(da1, gx) < 2e-2 and rel_err(da1, da1_u) < 2e-2
     assert rel_err(dw_f, tw.grad) < 1e-2 and rel_err(dw_f, dw_u) < 1e-2
     assert rel_err(dg_f, tg.grad) < 2e-2 and rel_err(db_f, tb.grad) < 2e-2
+
+
+@pytest.mark.parametrize("s", [1, 2])
+def test_dwconv_bn_bwd_refuses_no_gelu(s):
+    """The GELU is built into the depthwise + BatchNorm backward kernels: act = (..., False)
+    is refused by dwconv_bn_bwd and dwconv_bn_bwd_dz (KernelError) before anything is
+    launched, so the sinks stay all zero."""
+    from ssl_mae_amd import _lib
+    kk = KK()
+    Fr, H, C = 1, 7, 32
+    W = H
+    Ho = (H - 1) // s + 1
+    a1 = rnd(Fr * H * W, C, seed=186).to(torch.bfloat16).to(DEV)
+    m0, r0 = kk.bn_stats(a1)
+    act0 = (m0, r0, torch.ones(C, device=DEV), torch.zeros(C, device=DEV), False)
+    wdw = rnd(C, 9, seed=187, scale=0.3).to(DEV)
+    da2 = rnd(Fr * Ho * Ho, C, dtype=torch.bfloat16, seed=188, scale=1e-2).to(DEV)
+    dw, dg, db = torch.zeros(C, 9, device=DEV), torch.zeros(C, device=DEV), torch.zeros(C, device=DEV)
+    for fn in (kk.dwconv_bn_bwd, kk.dwconv_bn_bwd_dz):
+        with pytest.raises(_lib.KernelError):
+            fn(da2, a1, act0, wdw, dw, dg, db, Fr, H, W, C, stride=s)
+    torch.cuda.synchronize()
+    assert not dw.any() and not dg.any() and not db.any()
 
 
 @pytest.mark.parametrize("Kd,N", [(96, 392), (384, 520)])
