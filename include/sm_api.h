@@ -427,6 +427,47 @@ int sm_exit_step(const float* emb, const int32_t* active, int n, int B, int D, i
  * index list): active int32 [B] <- ascending s with decided[s] == 0, *count <- their number. */
 int sm_active_compact(const uint8_t* decided, int B, int32_t* active, int32_t* count, hipStream_t st);
 
+/* ---- feature-privacy evaluation (src/run_privacy.py:229-348 run_feature_privacy; csrc/privacy.hip),
+ * all fp32; 16-byte accesses when the shapes and pointers allow, scalar ones otherwise (same bits).
+ *
+ * sm_privacy_perturb (src/privacy/feature_noise.py:4-15, run_privacy.py:299-300): z [N][D] ->
+ * out [G][N][D], out[g] = (z + sigma_g n_g(r, c)) keep_g(r, c), 1 <= G <= SM_PRIVACY_MAX_CONFIGS,
+ * one launch that reads z once.  Noise first, then the 0/1 mask with no 1 / keep rescale;
+ * sigma_g <= 0 adds nothing and thresholds[g] == 0 keeps everything (both bit-exact).  sigmas,
+ * thresholds, seeds are HOST arrays of G.  The draws are a pure function of (seed, r, c):
+ *   s32 = lo32(seed) ^ hi32(seed);  rb = fmix32(s32 + r * 0x9E3779B1)
+ *   h_k = fmix32(fmix32(rb + K_k) + c * 0x7FEB352D),  K = {0x68E31DA4, 0xB5297A4D, 0x1B56C4E9}
+ *   u1 = ((h0 >> 8) + 1) 2^-24 in (0, 1], u2 = (h1 >> 8) 2^-24, n = sqrt(-2 ln u1) cos(2 pi u2)
+ *   keep = (uint64)h2 >= thresholds[g], thresholds[g] = min(round(ratio 2^32), 2^32) (> 2^32: -2)
+ * so slice g of a grid call equals a G = 1 call with the same (sigma, threshold, seed) bit for bit.
+ * N < 2^31. */
+#define SM_PRIVACY_MAX_CONFIGS 64
+int sm_privacy_perturb(const float* z, int64_t N, int D, int G, const float* sigmas, const uint64_t* thresholds,
+                       const uint64_t* seeds, float* out, hipStream_t st);
+/* Classification metrics of logits [rows][C], rows = S * N, the label of row i = labels[i % N]
+ * (int64 [N]); one wave per row, C <= SM_LOGITS_MAX_CLASSES (else -2).  Per row: loss = logsumexp(l)
+ * - l_y (nn.CrossEntropyLoss, run_privacy.py:312), entropy = -sum_j p_j log(p_j + 1e-12)
+ * (metrics_privacy.py:5-8), hit1 / hitk = rank_y < 1 / < k with rank_y = #{j : l_j > l_y} +
+ * #{j < y : l_j == l_y} (metrics_privacy.py:15-16, run_privacy.py:306; where torch leaves ties
+ * open the lower index wins, as sm_topk_frames).  A NaN or +inf logit (or a label outside [0, C))
+ * makes the row's loss NaN and the row a miss.  out fp64 [S][4] = sum loss, sum entropy, #hit1,
+ * #hitk over each segment's N rows, added in fp64 in a fixed order.  dlogits (nullable) [rows][C]
+ * <- (softmax(l) - onehot(y)) * grad_scale.  Workspace sm_logits_metrics_workspace_bytes(rows),
+ * 16-byte aligned (else -4). */
+#define SM_LOGITS_MAX_CLASSES 4096
+int64_t sm_logits_metrics_workspace_bytes(int64_t rows);
+int sm_logits_metrics(const float* logits, int64_t rows, int C, const int64_t* labels, int64_t N, int k,
+                      float* dlogits, float grad_scale, double* out, void* ws, int64_t ws_bytes, hipStream_t st);
+/* The attacker's hidden layer (src/privacy/attacker.py:11-15 nn.ReLU between two Linears):
+ * h[i] = max(pre[i], 0) (NaN stays NaN); backward dpre = dh * (h > 0) and db[c] = sum over the M
+ * rows of dpre[.][c] (the first Linear's bias gradient) in the same pass: fp32 partial sums over
+ * chunks of 32 rows, the chunks added in fp64 in a fixed order.  Workspace
+ * sm_relu_bias_bwd_workspace_bytes; M <= 32 * 65535. */
+int sm_relu_fwd(const float* pre, int64_t n, float* h, hipStream_t st);
+int64_t sm_relu_bias_bwd_workspace_bytes(int64_t M, int C);
+int sm_relu_bias_bwd(const float* dh, const float* h, int64_t M, int C, float* dpre, float* db, void* ws,
+                     int64_t ws_bytes, hipStream_t st);
+
 /* ---- optimizer (train_ssl_mae.py:163 AdamW, :87-89 GradScaler inf-skip) */
 int sm_nonfinite(const float* g, int64_t n, int* flag, hipStream_t st);
 /* p *= a (data-parallel gradient averaging after a SUM all-reduce) */

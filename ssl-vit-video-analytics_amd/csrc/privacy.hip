@@ -1,0 +1,391 @@
+// Feature-privacy evaluation (src/run_privacy.py:229-348 run_feature_privacy of the reference,
+// src/privacy/feature_noise.py, metrics_privacy.py, attacker.py): the video embeddings under
+// Gaussian noise and random feature masking, the head's utility numbers over the whole grid,
+// and the hidden layer of the attacker probe.  All fp32:
+//   privacy_perturb   out[g] = (z + sigma_g n_g(r, c)) keep_g(r, c) for G configurations, z read once
+//   logits_metrics    per row cross-entropy / entropy / top-1 / top-k (+ the softmax gradient),
+//                     summed per segment in fp64
+//   relu_fwd          h = max(pre, 0)
+//   relu_bias_bwd     dpre = dh (h > 0) and its column sums in one pass
+// No atomics, no LDS tiling, no MFMA; every reduction has a fixed partition and order, so no
+// result depends on the launch geometry.  Each kernel has a 16-byte form and a scalar form with
+// the same element ownership and summation order: same bits.
+#include "common.h"
+#include "sm_api.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+
+// ---------------------------------------------------------------- perturbation draws
+// Three 32-bit streams per (seed, row, col); the row and the column go through separate fmix32
+// rounds: rb = fmix32(seed32 + row * 0x9E3779B1) is a bijection of the row, rk_k = fmix32(rb + K_k)
+// its three stream keys, h_k = fmix32(rk_k + col * 0x7FEB352D) a bijection of the column within a
+// row.  Two elements share (h0, h1) only if two independent 32-bit conditions hold.
+constexpr uint32_t kRowMul = 0x9E3779B1u, kColMul = 0x7FEB352Du;
+constexpr uint32_t kStream0 = 0x68E31DA4u, kStream1 = 0xB5297A4Du, kStream2 = 0x1B56C4E9u;
+
+struct PerturbCfg {
+  uint64_t thr[SM_PRIVACY_MAX_CONFIGS];   // keep iff (uint64)h2 >= thr; 0 keeps all, 2^32 drops all
+  float sigma[SM_PRIVACY_MAX_CONFIGS];
+  uint32_t s32[SM_PRIVACY_MAX_CONFIGS];
+};
+
+struct RowKeys {
+  uint32_t k0, k1, k2;
+};
+SM_DEV RowKeys row_keys(uint32_t s32, uint32_t row) {
+  const uint32_t rb = fmix32(s32 + row * kRowMul);
+  return RowKeys{fmix32(rb + kStream0), fmix32(rb + kStream1), fmix32(rb + kStream2)};
+}
+
+// One element: noise first, then the 0/1 mask without a 1 / keep rescale (feature_noise.py:4-15).
+// sigma <= 0 and thr == 0 leave the value untouched (bit-exact).
+SM_DEV float perturb_one(float z, const RowKeys& rk, uint32_t col, float sigma, uint64_t thr) {
+  const uint32_t cm = col * kColMul;
+  float v = z;
+  if (sigma > 0.f) {
+    const uint32_t h0 = fmix32(rk.k0 + cm), h1 = fmix32(rk.k1 + cm);
+    const float u1 = (float)((h0 >> 8) + 1u) * 0x1p-24f;      // (0, 1], exact
+    const float u2x2 = (float)(h1 >> 8) * 0x1p-23f;           // 2 u2 in [0, 2), exact
+    const float n = sqrtf(-2.0f * logf(u1)) * cospif(u2x2);   // cos(2 pi u2); the sine branch is not used
+    v = fmaf(sigma, n, z);
+  }
+  if (thr != 0) {
+    const uint32_t h2 = fmix32(rk.k2 + cm);
+    v *= (uint64_t)h2 >= thr ? 1.0f : 0.0f;
+  }
+  return v;
+}
+
+// One thread per group of 4 consecutive elements (flat index 4 t .. 4 t + 3), every configuration
+// in turn.  VEC: D % 4 == 0, so a group lies in one row and moves as 16 bytes.
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void perturb_kernel(const float* __restrict__ z, int64_t total, int D, int G,
+                                                           PerturbCfg cfg, float* __restrict__ out) {
+  const int64_t e0 = (blockIdx.x * (int64_t)kThreads + threadIdx.x) * 4;
+  if (e0 >= total) return;
+  if constexpr (VEC) {
+    const uint32_t row = (uint32_t)(e0 / D), col = (uint32_t)(e0 % D);
+    const f32x4 x = *(const f32x4*)(z + e0);
+    for (int g = 0; g < G; ++g) {
+      const RowKeys rk = row_keys(cfg.s32[g], row);
+      f32x4 y;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) y[j] = perturb_one(x[j], rk, col + j, cfg.sigma[g], cfg.thr[g]);
+      __builtin_nontemporal_store(y, (f32x4*)(out + (int64_t)g * total + e0));
+    }
+  } else {
+    const int n = total - e0 < 4 ? (int)(total - e0) : 4;
+    float x[4];
+    uint32_t row[4], col[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t e = e0 + j;
+      row[j] = (uint32_t)(e / D);
+      col[j] = (uint32_t)(e % D);
+      x[j] = j < n ? z[e] : 0.f;
+    }
+    for (int g = 0; g < G; ++g) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < n)
+          out[(int64_t)g * total + e0 + j] = perturb_one(x[j], row_keys(cfg.s32[g], row[j]), col[j], cfg.sigma[g],
+                                                         cfg.thr[g]);
+    }
+  }
+}
+
+// ---------------------------------------------------------------- logits metrics
+SM_DEV int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// x where in == ~0, -inf where in == 0
+SM_DEV float pad_neg_inf(float x, int in) {
+  return __int_as_float((__float_as_int(x) & in) | ((int)0xFF800000 & ~in));
+}
+
+// One wave per row, four rows per block.  Lane l owns columns 256 j + 4 l + i (j < NG, i < 4):
+// NG 16-byte groups in registers.  rowvals [rows][4] = loss, entropy, hit1, hitk.
+template <int NG, bool VEC>
+__global__ __launch_bounds__(kThreads) void logits_rows_kernel(const float* __restrict__ logits, int64_t rows, int C,
+                                                               const int64_t* __restrict__ labels, int64_t N, int k,
+                                                               float* __restrict__ dlogits, float grad_scale,
+                                                               float* __restrict__ rowvals) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = blockIdx.x * (int64_t)(kThreads / 64) + (threadIdx.x >> 6);
+  if (r >= rows) return;                              // wave-uniform
+  const float* x = logits + r * C;
+  float v[NG][4];
+  // every load is unconditional (a slot past the row reads column 0 instead) and is then set to
+  // -inf with an integer mask: no load sits under a per-lane branch and no lane mask stays live
+#pragma unroll
+  for (int j = 0; j < NG; ++j) {
+    const int c0 = 256 * j + 4 * lane;
+    if constexpr (VEC) {
+      const int in = (c0 - C) >> 31;                    // all ones when c0 < C
+      const f32x4 a = *(const f32x4*)(x + (c0 & in));
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[j][i] = pad_neg_inf(a[i], in);
+    } else if (256 * j + 256 <= C) {                    // wave-uniform: a whole 256-column slab
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[j][i] = x[c0 + i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int in = (c0 + i - C) >> 31;
+        v[j][i] = pad_neg_inf(x[(c0 + i) & in], in);
+      }
+    }
+  }
+  const int64_t y64 = labels[r % N];
+  const bool y_ok = y64 >= 0 && y64 < C;
+  const int y = y_ok ? (int)y64 : -1;
+  const float lx = x[y_ok ? y : 0];                    // the label's logit: one wave-uniform load
+  const float ly = y_ok ? lx : NAN;
+  float m = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < NG; ++j)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) m = fmaxf(m, v[j][i]);
+  m = wave_max(m);
+  float s = 0.f;
+  int rank = 0;
+#pragma unroll
+  for (int j = 0; j < NG; ++j)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = 256 * j + 4 * lane + i;
+      const float l = v[j][i];
+      // rank of the label: larger logits, and equal ones at a lower index, come first
+      // (a padding slot holds -inf at c >= C > y: it never counts, and its exp is 0)
+      rank += (l > ly || (l == ly && c < y)) ? 1 : 0;
+      const float e = expf(l - m);                       // a NaN or +inf logit makes the sum NaN
+      s += e;
+      v[j][i] = e;
+    }
+  s = wave_sum(s);
+  rank = wave_sum_i(rank);
+  const float lse = m + logf(s);
+  const float inv = 1.0f / s;
+  float ent = 0.f;
+#pragma unroll
+  for (int j = 0; j < NG; ++j)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float p = v[j][i] * inv;
+      ent -= p * logf(p + 1e-12f);                      // metrics_privacy.py:7; padding: p = 0 adds 0
+      v[j][i] = p;
+    }
+  ent = wave_sum(ent);
+  if (dlogits) {
+    float* d = dlogits + r * C;
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+      const int c0 = 256 * j + 4 * lane;
+      float gq[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) gq[i] = (v[j][i] - (c0 + i == y ? 1.0f : 0.0f)) * grad_scale;
+      if constexpr (VEC) {
+        if (c0 < C) *(f32x4*)(d + c0) = f32x4{gq[0], gq[1], gq[2], gq[3]};
+      } else if (256 * j + 256 <= C) {                  // wave-uniform: a whole 256-column slab
+#pragma unroll
+        for (int i = 0; i < 4; ++i) d[c0 + i] = gq[i];
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (c0 + i < C) d[c0 + i] = gq[i];
+      }
+    }
+  }
+  if (lane == 0) {
+    const float loss = lse - ly;
+    const bool finite = fabsf(lse) < INFINITY && y_ok && ly == ly;   // false for NaN
+    float* o = rowvals + r * 4;
+    o[0] = loss;
+    o[1] = ent;
+    o[2] = finite && rank < 1 ? 1.f : 0.f;
+    o[3] = finite && rank < k ? 1.f : 0.f;
+  }
+}
+
+// out[s][q] = sum over the N rows of segment s of rowvals[.][q], fp64: thread t takes rows t,
+// t + 256, ... ascending, then the 256 partials are added in thread order.
+__global__ __launch_bounds__(kThreads) void logits_segments_kernel(const float* __restrict__ rowvals, int64_t N,
+                                                                   double* __restrict__ out) {
+  __shared__ double red[kThreads][4];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const float* base = rowvals + (int64_t)s * N * 4;
+  double a[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int64_t i = tid; i < N; i += kThreads) {
+    const f32x4 q = *(const f32x4*)(base + i * 4);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) a[c] += (double)q[c];
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) red[tid][c] = a[c];
+  __syncthreads();
+  if (tid < 4) {
+    double t = 0.0;
+    for (int i = 0; i < kThreads; ++i) t += red[i][tid];
+    out[(int64_t)s * 4 + tid] = t;
+  }
+}
+
+template <int NG>
+void launch_logits_rows(bool vec, unsigned grid, hipStream_t st, const float* logits, int64_t rows, int C,
+                        const int64_t* labels, int64_t N, int k, float* dlogits, float grad_scale, float* rowvals) {
+  if (vec)
+    hipLaunchKernelGGL((logits_rows_kernel<NG, true>), dim3(grid), dim3(kThreads), 0, st, logits, rows, C, labels, N, k,
+                       dlogits, grad_scale, rowvals);
+  else
+    hipLaunchKernelGGL((logits_rows_kernel<NG, false>), dim3(grid), dim3(kThreads), 0, st, logits, rows, C, labels, N,
+                       k, dlogits, grad_scale, rowvals);
+}
+
+// ---------------------------------------------------------------- ReLU
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void relu_fwd_kernel(const float* __restrict__ pre, int64_t n,
+                                                            float* __restrict__ h) {
+  const int64_t e0 = (blockIdx.x * (int64_t)kThreads + threadIdx.x) * 4;
+  if (e0 >= n) return;
+  auto relu = [](float x) { return x > 0.f ? x : (x == x ? 0.f : x); };   // NaN stays NaN
+  if constexpr (VEC) {
+    const f32x4 a = *(const f32x4*)(pre + e0);
+    *(f32x4*)(h + e0) = f32x4{relu(a[0]), relu(a[1]), relu(a[2]), relu(a[3])};
+  } else {
+    for (int j = 0; j < 4 && e0 + j < n; ++j) h[e0 + j] = relu(pre[e0 + j]);
+  }
+}
+
+// Block (one wave) = kReluRows rows x 256 columns, thread = 4 consecutive columns: dpre written,
+// the chunk's column sums to part [nchunks][C] (fp32, rows ascending); colred adds the chunks in fp64.
+constexpr int kReluRows = 32;
+
+template <bool VEC>
+__global__ __launch_bounds__(64) void relu_bias_bwd_kernel(const float* __restrict__ dh, const float* __restrict__ h,
+                                                           int64_t M, int C, float* __restrict__ dpre,
+                                                           float* __restrict__ part) {
+  const int c0 = (blockIdx.x * 64 + threadIdx.x) * 4;
+  if (c0 >= C) return;
+  const int64_t r0 = (int64_t)blockIdx.y * kReluRows;
+  const int64_t r1 = r0 + kReluRows < M ? r0 + kReluRows : M;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int64_t r = r0; r < r1; ++r) {
+    const int64_t o = r * C + c0;
+    if constexpr (VEC) {
+      const f32x4 g = *(const f32x4*)(dh + o), a = *(const f32x4*)(h + o);
+      f32x4 d;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        d[j] = a[j] > 0.f ? g[j] : 0.f;
+        acc[j] += d[j];
+      }
+      *(f32x4*)(dpre + o) = d;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (c0 + j < C) {
+          const float d = h[o + j] > 0.f ? dh[o + j] : 0.f;
+          dpre[o + j] = d;
+          acc[j] += d;
+        }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (c0 + j < C) part[(int64_t)blockIdx.y * C + c0 + j] = acc[j];
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" int sm_privacy_perturb(const float* z, int64_t N, int D, int G, const float* sigmas,
+                                  const uint64_t* thresholds, const uint64_t* seeds, float* out, hipStream_t st) {
+  if (N <= 0 || D <= 0 || G <= 0 || G > SM_PRIVACY_MAX_CONFIGS || N > 0x7fffffff || !z || !sigmas || !thresholds ||
+      !seeds || !out)
+    return -2;
+  const int64_t total = N * D;
+  const int64_t nblk = ((total + 3) / 4 + kThreads - 1) / kThreads;
+  if (nblk > 0x7fffffff) return -2;
+  PerturbCfg cfg{};
+  for (int g = 0; g < G; ++g) {
+    if (thresholds[g] > (1ull << 32)) return -2;
+    cfg.thr[g] = thresholds[g];
+    cfg.sigma[g] = sigmas[g];
+    cfg.s32[g] = (uint32_t)seeds[g] ^ (uint32_t)(seeds[g] >> 32);      // seed32
+  }
+  if (D % 4 == 0 && aligned16(z) && aligned16(out))
+    hipLaunchKernelGGL(perturb_kernel<true>, dim3((unsigned)nblk), dim3(kThreads), 0, st, z, total, D, G, cfg, out);
+  else
+    hipLaunchKernelGGL(perturb_kernel<false>, dim3((unsigned)nblk), dim3(kThreads), 0, st, z, total, D, G, cfg, out);
+  SM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int64_t sm_logits_metrics_workspace_bytes(int64_t rows) {
+  return rows > 0 ? rows * 4 * (int64_t)sizeof(float) : 0;
+}
+
+extern "C" int sm_logits_metrics(const float* logits, int64_t rows, int C, const int64_t* labels, int64_t N, int k,
+                                 float* dlogits, float grad_scale, double* out, void* ws, int64_t ws_bytes,
+                                 hipStream_t st) {
+  if (rows <= 0 || N <= 0 || rows % N || C <= 0 || C > SM_LOGITS_MAX_CLASSES || k <= 0 || !logits || !labels || !out)
+    return -2;
+  const int64_t S = rows / N;
+  const int64_t nblk = (rows + kThreads / 64 - 1) / (kThreads / 64);
+  if (nblk > 0x7fffffff || S > 0x7fffffff) return -2;
+  if (!ws || ws_bytes < sm_logits_metrics_workspace_bytes(rows) || !aligned16(ws)) return -4;
+  float* rowvals = (float*)ws;
+  const bool vec = C % 4 == 0 && aligned16(logits) && (!dlogits || aligned16(dlogits));
+  const unsigned grid = (unsigned)nblk;
+  if (C <= 256) launch_logits_rows<1>(vec, grid, st, logits, rows, C, labels, N, k, dlogits, grad_scale, rowvals);
+  else if (C <= 512) launch_logits_rows<2>(vec, grid, st, logits, rows, C, labels, N, k, dlogits, grad_scale, rowvals);
+  else if (C <= 1024) launch_logits_rows<4>(vec, grid, st, logits, rows, C, labels, N, k, dlogits, grad_scale, rowvals);
+  else if (C <= 2048) launch_logits_rows<8>(vec, grid, st, logits, rows, C, labels, N, k, dlogits, grad_scale, rowvals);
+  else launch_logits_rows<16>(vec, grid, st, logits, rows, C, labels, N, k, dlogits, grad_scale, rowvals);
+  SM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(logits_segments_kernel, dim3((unsigned)S), dim3(kThreads), 0, st, rowvals, N, out);
+  SM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sm_relu_fwd(const float* pre, int64_t n, float* h, hipStream_t st) {
+  if (n <= 0) return 0;
+  if (!pre || !h) return -2;
+  const int64_t nblk = ((n + 3) / 4 + kThreads - 1) / kThreads;
+  if (nblk > 0x7fffffff) return -2;
+  if (aligned16(pre) && aligned16(h) && n % 4 == 0)
+    hipLaunchKernelGGL(relu_fwd_kernel<true>, dim3((unsigned)nblk), dim3(kThreads), 0, st, pre, n, h);
+  else
+    hipLaunchKernelGGL(relu_fwd_kernel<false>, dim3((unsigned)nblk), dim3(kThreads), 0, st, pre, n, h);
+  SM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int64_t sm_relu_bias_bwd_workspace_bytes(int64_t M, int C) {
+  if (M <= 0 || C <= 0) return 0;
+  return ((M + kReluRows - 1) / kReluRows) * C * (int64_t)sizeof(float);
+}
+
+extern "C" int sm_relu_bias_bwd(const float* dh, const float* h, int64_t M, int C, float* dpre, float* db, void* ws,
+                                int64_t ws_bytes, hipStream_t st) {
+  if (M <= 0 || C <= 0 || !dh || !h || !dpre || !db) return -2;
+  const int64_t nchunks = (M + kReluRows - 1) / kReluRows;
+  if (nchunks > 65535) return -2;
+  if (!ws || ws_bytes < sm_relu_bias_bwd_workspace_bytes(M, C)) return -4;
+  float* part = (float*)ws;
+  const dim3 grid((unsigned)((C + 255) / 256), (unsigned)nchunks);
+  if (C % 4 == 0 && aligned16(dh) && aligned16(h) && aligned16(dpre))
+    hipLaunchKernelGGL(relu_bias_bwd_kernel<true>, grid, dim3(64), 0, st, dh, h, M, C, dpre, part);
+  else
+    hipLaunchKernelGGL(relu_bias_bwd_kernel<false>, grid, dim3(64), 0, st, dh, h, M, C, dpre, part);
+  SM_CHECK_LAUNCH();
+  colred(part, (int)nchunks, C, nullptr, db, 0, st);
+  SM_CHECK_LAUNCH();
+  return 0;
+}

@@ -154,6 +154,13 @@ _SIGS = {
     "sm_exit_step": (_c_i32, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_f32, _c_i32, _c_i32]
                      + [_c_p] * 6 + [_c_p]),
     "sm_active_compact": (_c_i32, [_c_p, _c_i32, _c_p, _c_p, _c_p]),
+    "sm_privacy_perturb": (_c_i32, [_c_p, _c_i64, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "sm_logits_metrics_workspace_bytes": (_c_i64, [_c_i64]),
+    "sm_logits_metrics": (_c_i32, [_c_p, _c_i64, _c_i32, _c_p, _c_i64, _c_i32, _c_p, _c_f32, _c_p, _c_p, _c_i64,
+                                   _c_p]),
+    "sm_relu_fwd": (_c_i32, [_c_p, _c_i64, _c_p, _c_p]),
+    "sm_relu_bias_bwd_workspace_bytes": (_c_i64, [_c_i64, _c_i32]),
+    "sm_relu_bias_bwd": (_c_i32, [_c_p, _c_p, _c_i64, _c_i32, _c_p, _c_p, _c_p, _c_i64, _c_p]),
 }
 
 _lib = None

@@ -1079,3 +1079,82 @@ def active_compact(decided, active, count):
     if decided.dtype != torch.uint8 or not decided.is_contiguous():
         raise _lib.KernelError("decided must be contiguous uint8 [B]")
     call("sm_active_compact", ptr(decided), B, ptr(active), ptr(count), stream())
+
+
+# ------------------------------------------------------------------ feature-privacy evaluation
+PRIVACY_MAX_CONFIGS = 64      # SM_PRIVACY_MAX_CONFIGS
+LOGITS_MAX_CLASSES = 4096     # SM_LOGITS_MAX_CLASSES
+
+
+def _f32_2d(t, what):
+    _chk(t)
+    if t.dim() != 2 or t.dtype != torch.float32 or not t.is_contiguous():
+        raise _lib.KernelError(f"{what} must be a contiguous fp32 matrix")
+
+
+def privacy_perturb(z, sigmas, thresholds, seeds):
+    """z fp32 [N,D] -> fp32 [G,N,D]: out[g] = (z + sigmas[g] * n_g) * keep_g, the draws a pure
+    function of (seeds[g], row, col) (include/sm_api.h).  thresholds[g] in [0, 2^32]: an element
+    is kept iff its 32-bit mask draw is >= the threshold."""
+    import ctypes
+    _f32_2d(z, "privacy_perturb: z")
+    G = len(sigmas)
+    if len(thresholds) != G or len(seeds) != G:
+        raise _lib.KernelError("privacy_perturb: sigmas, thresholds and seeds must have one entry per configuration")
+    N, D = z.shape
+    out = torch.empty((G, N, D), dtype=torch.float32, device=z.device)
+    sg = (ctypes.c_float * max(G, 1))(*[float(s) for s in sigmas])
+    th = (ctypes.c_uint64 * max(G, 1))(*[int(t) for t in thresholds])
+    sd = (ctypes.c_uint64 * max(G, 1))(*[int(s) & ((1 << 64) - 1) for s in seeds])
+    call("sm_privacy_perturb", ptr(z), N, D, G, ctypes.cast(sg, ctypes.c_void_p), ctypes.cast(th, ctypes.c_void_p),
+         ctypes.cast(sd, ctypes.c_void_p), ptr(out), stream())
+    return out
+
+
+def logits_metrics(logits, labels, k, segments=1, dlogits=None, grad_scale=1.0):
+    """logits fp32 [S*N, C], labels int64 [N] -> fp64 [S,4]: per segment sum of the cross-entropy,
+    sum of the entropy, top-1 hits, top-k hits.  dlogits (fp32, logits' shape, optional) receives
+    (softmax - onehot) * grad_scale."""
+    _f32_2d(logits, "logits_metrics: logits")
+    _chk(labels, dlogits)
+    rows, C = logits.shape
+    S = int(segments)
+    if labels.dtype != torch.int64 or labels.dim() != 1 or not labels.is_contiguous():
+        raise _lib.KernelError("logits_metrics: labels must be a contiguous int64 vector")
+    N = labels.numel()
+    if S < 1 or rows != S * N:
+        raise _lib.KernelError(f"logits_metrics: {rows} rows are not {S} segments of {N} labels")
+    if dlogits is not None and (dlogits.dtype != torch.float32 or dlogits.shape != logits.shape
+                                or not dlogits.is_contiguous()):
+        raise _lib.KernelError("logits_metrics: dlogits must match the logits (contiguous fp32)")
+    out = torch.empty((S, 4), dtype=torch.float64, device=logits.device)
+    nbytes = query("sm_logits_metrics_workspace_bytes", rows)
+    ws = _ws(nbytes, logits.device)
+    call("sm_logits_metrics", ptr(logits), rows, C, ptr(labels), N, int(k), ptr(dlogits), float(grad_scale), ptr(out),
+         ptr(ws), nbytes, stream())
+    return out
+
+
+def relu_fwd(pre):
+    """h = max(pre, 0), fp32."""
+    _chk(pre)
+    if pre.dtype != torch.float32 or not pre.is_contiguous():
+        raise _lib.KernelError("relu_fwd takes a contiguous fp32 tensor")
+    h = torch.empty_like(pre)
+    call("sm_relu_fwd", ptr(pre), pre.numel(), ptr(h), stream())
+    return h
+
+
+def relu_bias_bwd(dh, h, db):
+    """-> dpre = dh * (h > 0); db [C] <- the column sums of dpre (written, not accumulated)."""
+    _f32_2d(dh, "relu_bias_bwd: dh")
+    _f32_2d(h, "relu_bias_bwd: h")
+    _chk(db)
+    M, C = dh.shape
+    if h.shape != dh.shape or db.dtype != torch.float32 or db.numel() != C or not db.is_contiguous():
+        raise _lib.KernelError("relu_bias_bwd: h must match dh and db be contiguous fp32 [C]")
+    dpre = torch.empty_like(dh)
+    nbytes = query("sm_relu_bias_bwd_workspace_bytes", M, C)
+    ws = _ws(nbytes, dh.device)
+    call("sm_relu_bias_bwd", ptr(dh), ptr(h), M, C, ptr(dpre), ptr(db), ptr(ws), nbytes, stream())
+    return dpre

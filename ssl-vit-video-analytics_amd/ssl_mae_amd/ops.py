@@ -1363,6 +1363,58 @@ def active_compact(decided, active, count):
     torch.ops.ssl_mae.active_compact(decided, active, count)
 
 
+# ============================================================================ feature-privacy evaluation
+@_op("privacy_perturb", "(Tensor z, float[] sigmas, int[] thresholds, int[] seeds) -> Tensor")
+def _privacy_perturb(z, sigmas, thresholds, seeds):
+    return _K.privacy_perturb(z, sigmas, thresholds, [_u64(s) for s in seeds])
+
+
+_privacy_perturb.register_fake(lambda z, sigmas, thresholds, seeds: z.new_empty((len(sigmas),) + tuple(z.shape)))
+
+
+def privacy_perturb(z, sigmas, thresholds, seeds):
+    return torch.ops.ssl_mae.privacy_perturb(z, [float(s) for s in sigmas], [int(t) for t in thresholds],
+                                             [_s64(s) for s in seeds])
+
+
+@_op("logits_metrics", "(Tensor logits, Tensor labels, int k, int segments, Tensor(a!)? dlogits, float grad_scale) "
+                       "-> Tensor", ("dlogits",))
+def _logits_metrics(logits, labels, k, segments, dlogits, grad_scale):
+    return _K.logits_metrics(logits, labels, k, segments, dlogits, grad_scale)
+
+
+_logits_metrics.register_fake(lambda logits, labels, k, segments, dlogits, grad_scale: logits.new_empty(
+    (segments, 4), dtype=torch.float64))
+
+
+def logits_metrics(logits, labels, k, segments=1, dlogits=None, grad_scale=1.0):
+    return torch.ops.ssl_mae.logits_metrics(logits, labels, int(k), int(segments), dlogits, float(grad_scale))
+
+
+@_op("relu_fwd", "(Tensor pre) -> Tensor")
+def _relu_fwd(pre):
+    return _K.relu_fwd(pre)
+
+
+_relu_fwd.register_fake(lambda pre: torch.empty_like(pre))
+
+
+def relu_fwd(pre):
+    return torch.ops.ssl_mae.relu_fwd(pre)
+
+
+@_op("relu_bias_bwd", "(Tensor dh, Tensor h, Tensor(a!) db) -> Tensor", ("db",))
+def _relu_bias_bwd(dh, h, db):
+    return _K.relu_bias_bwd(dh, h, db)
+
+
+_relu_bias_bwd.register_fake(lambda dh, h, db: torch.empty_like(dh))
+
+
+def relu_bias_bwd(dh, h, db):
+    return torch.ops.ssl_mae.relu_bias_bwd(dh, h, db)
+
+
 def registered_ops():
     """Names of every ssl_mae operator registered by this module."""
     return sorted(n for n in dir(torch.ops.ssl_mae) if not n.startswith("_") and

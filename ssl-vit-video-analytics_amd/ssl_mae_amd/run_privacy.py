@@ -1,0 +1,198 @@
+"""Feature-privacy evaluation of a fine-tuned VideoClassifier: the utility-against-leakage
+curve of its video embeddings under Gaussian noise and random feature masking, with an
+auxiliary attacker classifier as the leakage probe (reference src/run_privacy.py:229-348
+run_feature_privacy), MI355X-native.
+
+    PYTHONPATH=ssl-vit-video-analytics_amd python -m ssl_mae_amd.run_privacy \
+        --config configs/privacy.yaml [--ckpt model.pth] [--save_dir results/privacy]
+
+The embeddings, labels and clean logits are extracted once; the whole noise x mask grid then
+takes three launches for its utility numbers (privacy.perturb_grid, one head GEMM over G * N
+rows, privacy.logits_metrics with G segments) and one freshly initialised attacker per
+configuration, trained one after another (privacy.train_attacker).  `feature_privacy.csv` has
+the reference's columns and rounding.  `runtime.amp` governs only the backbone pass; the sweep
+is always fp32.  Without `dataset.split` the driver runs on synthetic clips (random labels:
+the accuracy columns then only show chance).
+
+The reference's visual half (YuNet face detection + cv2.GaussianBlur, :118-226) needs OpenCV
+and a downloaded detector; it is not part of this build.  An enabled `visual_privacy` section
+is accepted, logged and skipped.
+"""
+import argparse
+import time
+from pathlib import Path
+
+import torch
+
+from . import privacy as P
+from .finetune import VideoClassifier
+from .run_dynamic import SyntheticLoader, load_finetune_ckpt, split_loader
+from .utils import load_config, set_seed
+
+CSV_COLUMNS = ("sigma", "mask_ratio", "top1", "top5", "entropy", "attacker_top1", "per_vs_clean")
+CSV_HEADER = ",".join(CSV_COLUMNS) + "\n"
+
+DEFAULTS = {
+    "dataset": {"name": None, "split": None, "num_classes": 101, "clip_len": 16, "stride": 4, "image_size": 112},
+    "model": {"embed_dim": 576, "finetune_ckpt": None},
+    # the reference's keys, accepted so its config loads; the stage itself is skipped
+    "visual_privacy": {"enabled": False, "frame_root": None, "max_images": 2000, "save_examples": 8,
+                       "detector": "yunet", "yunet_model": None, "yunet_url": None, "conf_threshold": 0.6,
+                       "nms_threshold": 0.3, "method": "face_blur", "blur_kernel": 31, "overwrite": False,
+                       "output_suffix": "_frames_privacy"},
+    "feature_privacy": {"enabled": True, "noise_sigmas": [0.0, 0.05, 0.1, 0.2], "mask_ratios": [0.0, 0.2, 0.4],
+                        "attacker_epochs": 10, "attacker_lr": 1e-3},
+    "runtime": {"batch_size": 16, "num_batches": 6, "amp": True, "seed": 42, "num_workers": 4},
+    "output": {"save_dir": "results/privacy"},
+}
+
+
+def resolve_config(cfg, ckpt=None, save_dir=None):
+    """The file's values over DEFAULTS, the command line over both; unknown sections or keys
+    raise, the two grid lists are coerced to float and must not be empty."""
+    out = {sec: dict(vals) for sec, vals in DEFAULTS.items()}
+    for sec, vals in (cfg or {}).items():
+        if sec not in out:
+            raise ValueError(f"[ERROR] Unknown config section: {sec}")
+        unknown = set(vals or {}) - set(out[sec])
+        if unknown:
+            raise ValueError(f"[ERROR] Unknown keys in {sec}: {sorted(unknown)}")
+        out[sec].update(vals or {})
+    if ckpt is not None:
+        out["model"]["finetune_ckpt"] = ckpt
+    if save_dir is not None:
+        out["output"]["save_dir"] = save_dir
+    fp = out["feature_privacy"]
+    for key in ("noise_sigmas", "mask_ratios"):
+        vals = fp[key]
+        if not isinstance(vals, (list, tuple)) or len(vals) == 0:
+            raise ValueError(f"[ERROR] feature_privacy.{key} needs at least one entry")
+        fp[key] = [float(v) for v in vals]
+    if len(fp["noise_sigmas"]) * len(fp["mask_ratios"]) > 64:
+        raise ValueError("[ERROR] at most 64 (sigma, mask_ratio) configurations per sweep")
+    fp["attacker_epochs"] = int(fp["attacker_epochs"])
+    fp["attacker_lr"] = float(fp["attacker_lr"])
+    if fp["attacker_epochs"] < 0 or int(out["runtime"]["num_batches"]) < 1:
+        raise ValueError("[ERROR] attacker_epochs >= 0 and runtime.num_batches >= 1")
+    return out
+
+
+def format_row(row):
+    """One CSV line with the reference's rounding (run_privacy.py:329-337)."""
+    vals = [float(row["sigma"]), float(row["mask_ratio"])] + [round(float(row[c]), 6) for c in CSV_COLUMNS[2:]]
+    return ",".join(str(v) for v in vals) + "\n"
+
+
+def _log(log_f, msg):
+    print(msg)
+    log_f.write(msg + "\n")
+    log_f.flush()
+
+
+def run_visual_privacy(cfg, log_f):
+    if cfg["visual_privacy"]["enabled"]:
+        _log(log_f, "[INFO] visual_privacy needs OpenCV (YuNet face detection + GaussianBlur) and is not part of "
+                    "this build -> skip")
+
+
+def _loader(cfg, device):
+    if cfg["dataset"]["split"]:
+        shim = {"dataset": cfg["dataset"], "runtime": cfg["runtime"]}
+        return split_loader(shim, device)
+    rt = cfg["runtime"]
+    shim = {"dataset": cfg["dataset"], "runtime": {"batch_size": rt["batch_size"], "num_warmup": 0,
+                                                   "num_measure": rt["num_batches"], "seed": rt["seed"]}}
+    return SyntheticLoader(shim, device)
+
+
+@torch.no_grad()
+def extract_embeddings(model, loader, cfg):
+    """-> (z [N, D], y [N], clean logits [N, C]) on the device (run_privacy.py:264-280)."""
+    zs, ys, ls = [], [], []
+    for clip, label in loader:
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bool(cfg["runtime"]["amp"])):
+            z = P.video_embeddings(model, clip)
+        zs.append(z)
+        ys.append(label.long())
+        ls.append(model.classifier(z))
+    return torch.cat(zs), torch.cat(ys), torch.cat(ls)
+
+
+def run_feature_privacy(model, loader, device, cfg, log_f):
+    """-> {"rows", "clean_top1", "clean_entropy", "embed_s", "sweep_s", "csv"}."""
+    fp = cfg["feature_privacy"]
+    save_dir = Path(cfg["output"]["save_dir"])
+    out_csv = save_dir / "feature_privacy.csv"
+    if not fp["enabled"]:
+        _log(log_f, "[INFO] feature_privacy disabled -> skip")
+        return {"rows": [], "csv": out_csv}
+    nc = int(cfg["dataset"]["num_classes"])
+    k5 = min(5, nc)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    z, y, logits_clean = extract_embeddings(model, loader, cfg)
+    _, ent, top1, _ = P.logits_metrics(logits_clean, y, k5)
+    clean_top1, clean_ent = top1.item(), ent.item()
+    t1 = time.perf_counter()
+    _log(log_f, f"[INFO] Clean embeddings -> Top-1={clean_top1:.4f}, Entropy={clean_ent:.4f}")
+
+    P.route_head(model)                          # model.classifier on the project's GEMM
+    cfgs = P.grid_configs(fp["noise_sigmas"], fp["mask_ratios"], int(cfg["runtime"]["seed"]))
+    G, (N, D) = len(cfgs), z.shape
+    with torch.no_grad():
+        z_priv = P.perturb_grid(z, fp["noise_sigmas"], fp["mask_ratios"], int(cfg["runtime"]["seed"]))
+        _, g_ent, g_top1, g_top5 = P.logits_metrics(model.classifier(z_priv.view(G * N, D)), y, k5, segments=G)
+        atk = []
+        for g in range(G):                       # one fresh attacker per configuration, one after another
+            attacker = P.FeatureAttacker(D, nc).to(device)
+            P.train_attacker(attacker, z_priv[g], y, fp["attacker_epochs"], fp["attacker_lr"])
+            atk.append(P.logits_metrics(attacker(z_priv[g]), y, 1)[2])
+        util = torch.stack([g_top1, g_top5, g_ent, torch.cat(atk)], dim=1).cpu().tolist()   # the sweep's one readback
+    t2 = time.perf_counter()
+
+    rows, lines = [], [CSV_HEADER]
+    for (sigma, ratio, _), (t1_, t5_, e_, a_) in zip(cfgs, util):
+        row = {"sigma": sigma, "mask_ratio": ratio, "top1": t1_, "top5": t5_, "entropy": e_, "attacker_top1": a_,
+               "per_vs_clean": P.privacy_exposure_rate(clean_top1, a_)}
+        rows.append(row)
+        lines.append(format_row(row))
+        _log(log_f, f"[INFO] sigma={sigma} mask={ratio} | top1={t1_:.4f} top5={t5_:.4f} | attacker={a_:.4f} | "
+                    f"ent={e_:.4f}")
+    out_csv.write_text("".join(lines), encoding="utf-8")
+    _log(log_f, f"[INFO] Saved feature privacy CSV: {out_csv}")
+    _log(log_f, f"[INFO] embedding pass {t1 - t0:.3f} s ({N} clips), sweep {t2 - t1:.3f} s ({G} configurations)")
+    return {"rows": rows, "clean_top1": clean_top1, "clean_entropy": clean_ent, "embed_s": t1 - t0,
+            "sweep_s": t2 - t1, "csv": out_csv}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Privacy evaluation (feature noise / mask sweep with attacker probe).")
+    ap.add_argument("--config", default="configs/privacy.yaml")
+    ap.add_argument("--ckpt", default=None, help="override model.finetune_ckpt")
+    ap.add_argument("--save_dir", default=None, help="override output.save_dir")
+    args = ap.parse_args(argv)
+    cfg = resolve_config(load_config(args.config), args.ckpt, args.save_dir)
+    set_seed(cfg["runtime"]["seed"])
+    if not torch.cuda.is_available():
+        raise RuntimeError("[ERROR] run_privacy needs an MI355X: the HIP kernels have no CPU fallback")
+    device = torch.device("cuda")
+    from .build import build
+    build()
+    save_dir = Path(cfg["output"]["save_dir"])
+    save_dir.mkdir(parents=True, exist_ok=True)
+    with open(save_dir / "privacy.log", "a", encoding="utf-8") as log_f:
+        _log(log_f, "[INFO] Privacy evaluation started")
+        run_visual_privacy(cfg, log_f)
+        result = {"rows": []}
+        if cfg["feature_privacy"]["enabled"]:
+            model = VideoClassifier(int(cfg["dataset"]["num_classes"]), embed_dim=int(cfg["model"]["embed_dim"]),
+                                    img_size=int(cfg["dataset"]["image_size"]))
+            load_finetune_ckpt(model, cfg["model"]["finetune_ckpt"])
+            model.to(device).eval()
+            result = run_feature_privacy(model, _loader(cfg, device), device, cfg, log_f)
+        _log(log_f, "[INFO] Privacy evaluation finished.")
+    return result
+
+
+if __name__ == "__main__":
+    main()
