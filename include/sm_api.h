@@ -468,6 +468,46 @@ int64_t sm_relu_bias_bwd_workspace_bytes(int64_t M, int C);
 int sm_relu_bias_bwd(const float* dh, const float* h, int64_t M, int C, float* dpre, float* db, void* ws,
                      int64_t ws_bytes, hipStream_t st);
 
+/* ---- MAE reconstruction evaluation (src/visualize_mae.py:162-208, the token-error map of
+ * src/mae/visualize.py:47-58; csrc/recon.hip).  p = 8, C = 3 as the loss; H % 8 or W % 8: -2.
+ *
+ * sm_mae_reconstruct: one launch over pred [B][T*L][192] (fp32 or bf16 by pred_dtype, as
+ * sm_mae_loss_fwd), clip fp32 [B][3][T][H][W] through its five element strides and mask uint8
+ * [B][T][L]; the target and the reconstruction are never stored as token tensors.  Per token, x
+ * the 192 clip values of its patch in feature order f = (p * 8 + q) * 3 + c:
+ *   target   norm_pix: mu = mean(x), var = sum((x - mu)^2) / 191, tgt = (x - mu) / sqrt(var + 1e-6)
+ *            (the loss's operations, train_ssl_mae.py:74-77); otherwise tgt = x
+ *   recon    r = pred * sqrt(var + 1e-6) + mu (norm_pix) or pred: the prediction in clip space;
+ *            with paste_visible a visible token (mask == 0) shows r = x instead
+ *   display  clip channel c is source channel s = 2 - c when bgr_swap, else c (the inverse of
+ *            sm_frames_normalize); v = value * std3[s] + mean3[s], written at RGB position s
+ *   byte     floor(clamp(v, 0, 1) * 255), the reference's (x * 255).astype(uint8)
+ * Outputs:
+ *   panels    uint8 [B][T][H][3 * W][3]: original | masked original | reconstruction, HWC RGB
+ *             strips ready for an image file; the pixels of masked patches are 0 in the middle panel
+ *   recon     (nullable) fp32 [B][3][T][H][W], dense: the display value v of the reconstruction,
+ *             not clamped, RGB channel order
+ *   token_err fp32 [B * T * L][2]: [0] = mean_f (pred - tgt)^2, the loss map entry
+ *             (train_ssl_mae.py:81-82); [1] = mean_f (clamp(v_r, 0, 1) - clamp(v_x, 0, 1))^2 with
+ *             v_r from r before paste_visible and v_x from x (where neither clamps, the difference
+ *             is formed as (pred - tgt) sqrt(var + 1e-6) std3[s], which does not cancel)
+ * mean3 / std3 are HOST arrays of 3 floats indexed by RGB position.  One wave per four tokens,
+ * fixed reduction order, no atomics: bitwise reproducible.  The panels are stored as packed
+ * dwords when their base is 4-byte aligned, as bytes otherwise (same bits).  T * L < 2^31 and
+ * B * T * L < 2^35 (else -2); a null pred, clip, mask, mean3, std3,
+ * panels or token_err, or a pred_dtype that is neither, is -2; nothing is launched on -2.
+ *
+ * sm_recon_clip_metrics: token_err and mask as above -> out fp32 [B][4] = mean of token_err[.][0]
+ * over the clip's masked tokens, mean of token_err[.][1] over them (mse_pix), PSNR =
+ * 10 log10(1 / mse_pix) dB, n_masked.  n_masked == 0 gives means 0; mse_pix == 0 gives PSNR +inf.
+ * One block per clip, fp64 sums in a fixed order, no atomics: bitwise reproducible. */
+int sm_mae_reconstruct(int pred_dtype, const void* pred, const float* clip, int64_t sB, int64_t sC, int64_t sT,
+                       int64_t sH, int64_t sW, const uint8_t* mask, int B, int T, int H, int W, const float* mean3,
+                       const float* std3, int norm_pix, int paste_visible, int bgr_swap, uint8_t* panels,
+                       float* recon, float* token_err, hipStream_t st);
+int sm_recon_clip_metrics(const float* token_err, const uint8_t* mask, int B, int T, int L, float* out,
+                          hipStream_t st);
+
 /* ---- optimizer (train_ssl_mae.py:163 AdamW, :87-89 GradScaler inf-skip) */
 int sm_nonfinite(const float* g, int64_t n, int* flag, hipStream_t st);
 /* p *= a (data-parallel gradient averaging after a SUM all-reduce) */

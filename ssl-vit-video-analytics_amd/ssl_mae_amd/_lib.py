@@ -161,6 +161,9 @@ _SIGS = {
     "sm_relu_fwd": (_c_i32, [_c_p, _c_i64, _c_p, _c_p]),
     "sm_relu_bias_bwd_workspace_bytes": (_c_i64, [_c_i64, _c_i32]),
     "sm_relu_bias_bwd": (_c_i32, [_c_p, _c_p, _c_i64, _c_i32, _c_p, _c_p, _c_p, _c_i64, _c_p]),
+    "sm_mae_reconstruct": (_c_i32, [_c_i32, _c_p, _c_p] + [_c_i64] * 5 + [_c_p] + [_c_i32] * 4 + [_c_p, _c_p]
+                           + [_c_i32] * 3 + [_c_p] * 4),
+    "sm_recon_clip_metrics": (_c_i32, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p]),
 }
 
 _lib = None

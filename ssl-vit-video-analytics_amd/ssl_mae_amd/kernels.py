@@ -1158,3 +1158,54 @@ def relu_bias_bwd(dh, h, db):
     ws = _ws(nbytes, dh.device)
     call("sm_relu_bias_bwd", ptr(dh), ptr(h), M, C, ptr(dpre), ptr(db), ptr(ws), nbytes, stream())
     return dpre
+
+
+# ------------------------------------------------------------------ MAE reconstruction evaluation
+def mae_reconstruct(pred, clip, mask_u8, mean, std, norm_pix=True, paste_visible=True, bgr_swap=True,
+                    want_recon=True):
+    """pred [B,T*L,192] (fp32 / bf16), clip fp32 [B,3,T,H,W] (any strides), mask uint8 [B,T,L] ->
+    (panels uint8 [B,T,H,3W,3], recon fp32 [B,3,T,H,W] or an empty tensor, token_err fp32 [B*T*L,2])
+    (include/sm_api.h); mean / std are the three display constants by RGB position."""
+    import ctypes
+    _chk(pred, clip, mask_u8)
+    if clip.dim() != 5 or clip.shape[1] != 3 or clip.dtype != torch.float32:
+        raise _lib.KernelError("mae_reconstruct takes an fp32 [B,3,T,H,W] clip")
+    B, T, H, W, sB, sC, sT, sH, sW = _clip_args(clip)
+    L = (H // 8) * (W // 8)
+    if pred.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.KernelError(f"mae_reconstruct: pred must be fp32 or bf16, not {pred.dtype}")
+    if clip.device != pred.device or mask_u8.device != pred.device:
+        raise _lib.KernelError("mae_reconstruct: pred, clip and mask must be on one device")
+    if not pred.is_contiguous() or pred.numel() != B * T * L * 192:
+        raise _lib.KernelError(f"mae_reconstruct: pred must be contiguous [{B},{T * L},192]")
+    if mask_u8.dtype != torch.uint8 or not mask_u8.is_contiguous() or mask_u8.numel() != B * T * L:
+        raise _lib.KernelError(f"mae_reconstruct: mask must be contiguous uint8 [{B},{T},{L}]")
+    if len(mean) != 3 or len(std) != 3:
+        raise _lib.KernelError("mae_reconstruct: mean and std have three entries")
+    dev = pred.device
+    panels = torch.empty((B, T, H, 3 * W, 3), dtype=torch.uint8, device=dev)
+    recon = torch.empty((B, 3, T, H, W) if want_recon else (0,), dtype=torch.float32, device=dev)
+    token_err = torch.empty((B * T * L, 2), dtype=torch.float32, device=dev)
+    m = (ctypes.c_float * 3)(*[float(x) for x in mean])
+    s = (ctypes.c_float * 3)(*[float(x) for x in std])
+    call("sm_mae_reconstruct", dt(pred), ptr(pred), ptr(clip), sB, sC, sT, sH, sW, ptr(mask_u8), B, T, H, W,
+         ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p), 1 if norm_pix else 0,
+         1 if paste_visible else 0, 1 if bgr_swap else 0, ptr(panels), ptr(recon) if want_recon else None,
+         ptr(token_err), stream())
+    return panels, recon, token_err
+
+
+def recon_clip_metrics(token_err, mask_u8):
+    """token_err fp32 [B*T*L,2], mask uint8 [B,T,L] -> fp32 [B,4]: masked-mean normalised error,
+    masked-mean pixel error, PSNR dB, n_masked."""
+    _chk(token_err, mask_u8)
+    if mask_u8.dim() != 3 or mask_u8.dtype != torch.uint8 or not mask_u8.is_contiguous():
+        raise _lib.KernelError("recon_clip_metrics: mask must be contiguous uint8 [B,T,L]")
+    B, T, L = mask_u8.shape
+    if token_err.device != mask_u8.device:
+        raise _lib.KernelError("recon_clip_metrics: token_err and mask must be on one device")
+    if token_err.dtype != torch.float32 or not token_err.is_contiguous() or token_err.numel() != B * T * L * 2:
+        raise _lib.KernelError(f"recon_clip_metrics: token_err must be contiguous fp32 [{B * T * L},2]")
+    out = torch.empty((B, 4), dtype=torch.float32, device=token_err.device)
+    call("sm_recon_clip_metrics", ptr(token_err), ptr(mask_u8), B, T, L, ptr(out), stream())
+    return out

@@ -1415,6 +1415,39 @@ def relu_bias_bwd(dh, h, db):
     return torch.ops.ssl_mae.relu_bias_bwd(dh, h, db)
 
 
+# ============================================================================ MAE reconstruction evaluation
+@_op("mae_reconstruct", "(Tensor pred, Tensor clip, Tensor mask, float[] mean, float[] std, bool norm_pix, "
+                        "bool paste_visible, bool bgr_swap, bool want_recon) -> (Tensor, Tensor, Tensor)")
+def _mae_reconstruct(pred, clip, mask, mean, std, norm_pix, paste_visible, bgr_swap, want_recon):
+    return _K.mae_reconstruct(pred, clip, mask, mean, std, norm_pix, paste_visible, bgr_swap, want_recon)
+
+
+@_mae_reconstruct.register_fake
+def _(pred, clip, mask, mean, std, norm_pix, paste_visible, bgr_swap, want_recon):
+    B, _, T, H, W = clip.shape
+    return (pred.new_empty((B, T, H, 3 * W, 3), dtype=torch.uint8),
+            pred.new_empty((B, 3, T, H, W) if want_recon else (0,), dtype=torch.float32),
+            pred.new_empty((B * T * (H // 8) * (W // 8), 2), dtype=torch.float32))
+
+
+def mae_reconstruct(pred, clip, mask_u8, mean, std, norm_pix=True, paste_visible=True, bgr_swap=True,
+                    want_recon=True):
+    return torch.ops.ssl_mae.mae_reconstruct(pred, clip, mask_u8, [float(x) for x in mean], [float(x) for x in std],
+                                             bool(norm_pix), bool(paste_visible), bool(bgr_swap), bool(want_recon))
+
+
+@_op("recon_clip_metrics", "(Tensor token_err, Tensor mask) -> Tensor")
+def _recon_clip_metrics(token_err, mask):
+    return _K.recon_clip_metrics(token_err, mask)
+
+
+_recon_clip_metrics.register_fake(lambda token_err, mask: token_err.new_empty((mask.shape[0], 4)))
+
+
+def recon_clip_metrics(token_err, mask_u8):
+    return torch.ops.ssl_mae.recon_clip_metrics(token_err, mask_u8)
+
+
 def registered_ops():
     """Names of every ssl_mae operator registered by this module."""
     return sorted(n for n in dir(torch.ops.ssl_mae) if not n.startswith("_") and
