@@ -31,8 +31,9 @@ extern "C" {
  * C = alpha*op(A)op(B) + bias (+ beta*R, R = C when null); epi bit0 = exact GELU
  * (aux <- pre-activation), bit1 = round the branch to bf16 before adding R (autocast).
  * Branch regularisers of the training step: elementwise dropout (drop_p, counter-hash
- * RNG keyed by seed and the element index, nn.Dropout semantics: keep w.p. 1-p, scale
- * 1/(1-p)) and DropPath (branch *= row_scale[row / rows_per_group]).
+ * RNG keyed by seed and the element index, nn.Dropout semantics with the keep rate quantised
+ * to 8 bits: dropped w.p. round(256 p)/256, kept values scaled by drop_scale(p) =
+ * 256/(256 - round(256 p))) and DropPath (branch *= row_scale[row / rows_per_group]).
  * a_layout 0: A[M][K], 1: A[K][M];  b_layout 0: B[N][K], 1: B[K][N]. */
 int64_t sm_gemm_workspace_bytes(int ab_dtype, int M, int N, int K);
 int sm_gemm(int ab_dtype, int c_dtype, int a_layout, int b_layout, int M, int N, int K,
@@ -66,7 +67,7 @@ int sm_linear_dw_bias(int rows, int nout, int nin, const void* dy, const void* x
                       int accumulate, void* ws, int64_t ws_bytes, hipStream_t stream);
 /* The fc2 data gradient through dropout(GELU(pre)) with the fc2 weight gradient's operand
  * as a side output (Mlp tiny_vit.py:74-84, decoder FF mae_vit_adapter.py:40-48): dx = (dy w)
- * * keep / (1 - p) * GELU'(pre) and h = bf16(GELU(pre) * keep / (1 - p)) (= sm_gelu_fwd(pre))
+ * * keep * drop_scale(p) * GELU'(pre) and h = bf16(GELU(pre) * keep * drop_scale(p)) (= sm_gelu_fwd(pre))
  * from one epilogue.  dy [M][N], w [N][K], pre / dx / h [M][K] bf16; N, K % 8 == 0. */
 int sm_linear_dx_gelu(int M, int N, int K, const void* dy, const void* w, const void* pre, void* dx, void* h,
                       float drop_p, uint64_t seed, hipStream_t stream);
@@ -157,7 +158,11 @@ int sm_mbconv_fold_dw(int mid, int Cin, int64_t M, const float* vec, const void*
 
 /* ---- fused attention (tiny_vit.py:103 F.scaled_dot_product_attention;
  * torch MultiheadAttention core of the decoder, mae_vit_adapter.py:40-48).
- * qkv packed [N][L][3][H][D] bf16|f32, out O [N][L][H][D], lse [N][H][L]. */
+ * qkv packed [N][L][3][H][D] bf16|f32, out O [N][L][H][D], lse [N][H][L].  D = 32 or 64
+ * (else -2).  drop_p > 0: dropout on the attention probabilities, mask a pure function of
+ * (seed, n, head, query, key) with the keep rate quantised to 7 bits: dropped w.p.
+ * round(128 p)/128, kept probabilities scaled by 128/(128 - round(128 p)); sm_attn_bwd
+ * regenerates the same mask from the same (drop_p, seed). */
 int sm_attn_fwd(int dtype, int N, int L, int H, int D, const void* qkv, void* out, float* lse,
                 float scale, float drop_p, uint64_t seed, hipStream_t st);
 /* delta_ws: workspace of sm_attn_bwd_workspace_bytes (256-B aligned): rowsum(dO * O)
@@ -231,11 +236,11 @@ int sm_gelu_fwd(int dtype, int64_t n, int ncols, const void* x, void* y, float d
 int sm_dropout_bwd(int dtype, int64_t n, int ncols, const void* dy, void* dx, float drop_p, uint64_t seed,
                    const float* row_scale, int64_t rows_per_group, hipStream_t st);
 /* sm_cast (fp32 -> bf16) and sm_dropout_bwd in one pass: dx_bf16 = bf16(bf16(dy) *
- * row_scale * keep / (1 - p)); the decoder block's fp32 residual-stream gradient entering
+ * row_scale * keep * drop_scale(p)); the decoder block's fp32 residual-stream gradient entering
  * its bf16 branch (torch.autocast's cast + nn.Dropout backward, mae_vit_adapter.py:40-48). */
 int sm_cast_dropout_bwd(int64_t n, int ncols, const float* dy, void* dx_bf16, float drop_p, uint64_t seed,
                         const float* row_scale, int64_t rows_per_group, hipStream_t st);
-/* DropPath per-sample keep scales: out[i] = keep ? 1/(1-p) : 0 */
+/* DropPath per-sample keep scales: out[i] = keep ? drop_scale(p) = 256/(256 - round(256 p)) : 0 */
 int sm_droppath_scale(int n, float p, uint64_t seed, float* out, hipStream_t st);
 /* column sums (Linear bias gradients): out[c] (+)= sum_m x[m][c] */
 int64_t sm_colsum_workspace_bytes(int64_t M, int C);

@@ -62,7 +62,7 @@ struct GemmArgs {
   // as dW^T = x^T dy, sm_linear_dw_bias)
   int ctrans;
   // IMP 9 only (sm_linear_dx_gelu): side output of the GELU input aux, aux_out = bf16(GELU(aux)
-  // * dropout keep / (1 - p)) = sm_gelu_fwd(aux) -- the fc2 weight gradient's operand
+  // * dropout keep * drop_scale(p)) = sm_gelu_fwd(aux) -- the fc2 weight gradient's operand
   void* aux_out;
   // IMP 14 only (sm_linear_dx2): a K-major A operand made of two K segments, columns [0, k1)
   // from A (ld lda) and columns [k1, K) from A2 (ld lda2); k1 % BKT == 0, so a K-step lies in
@@ -341,7 +341,7 @@ SM_DEV __attribute__((always_inline)) void gemm_epilogue(const GemmArgs& g, f32x
           if (g.epi & 2) v[e] = (float)(__bf16)v[e];
         }
         const int64_t idx = row * g.ldc + col;
-        float hg[8];       // AUXS side output: GELU(pre) (x keep / (1 - p) below)
+        float hg[8];       // AUXS side output: GELU(pre) (x keep * drop_scale(p) below)
         if (g.epi & 4) {   // GELU backward: the saved pre-activation run of this (row, cols)
           float pre[8];
           if (AUXS && sizeof(TC) == 2 && stage) {
@@ -2177,7 +2177,7 @@ static int gemm_run(int ab_dtype, int c_dtype, int a_layout, int b_layout, int M
 
 // fc2 data gradient through dropout(GELU(pre)) plus the fc2 weight gradient's operand
 // (tiny_vit.py:74-84 Mlp / mae_vit_adapter.py:40-48 decoder FF backward): dx = (dy w) *
-// keep / (1 - p) * GELU'(pre) and h = bf16(GELU(pre) * keep / (1 - p)) (bit-identical to
+// keep * drop_scale(p) * GELU'(pre) and h = bf16(GELU(pre) * keep * drop_scale(p)) (bit-identical to
 // sm_gelu_fwd(pre)) from one epilogue that reads pre once -- no recompute pass of h.
 // dy [M][N], w [N][K], pre / dx / h [M][K] bf16; K % 8 == 0, N % 8 == 0.
 extern "C" int sm_linear_dx_gelu(int M, int N, int K, const void* dy, const void* w, const void* pre, void* dx,

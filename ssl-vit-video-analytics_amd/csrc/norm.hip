@@ -202,7 +202,7 @@ __global__ __launch_bounds__(256) void ln_fwd16_kernel(const TI* x, const float*
 // dx (+ dres) and per-block partial dgamma / dbeta (part_g/part_b [block][C]).
 // Branch copy (bo != null): the transformer block's backward feeds dx to the residual
 // stream AND, through the branch regularisers' backward, to the branch's Linear:
-// bo = bf16(bf16(dx) * rs[row / rpg] * keep(row, col) / (1 - p)), i.e. the cast
+// bo = bf16(bf16(dx) * rs[row / rpg] * keep(row, col) * drop_scale(p)), i.e. the cast
 // (fp32 stream) and sm_dropout_bwd passes over dx folded into this one (same mask,
 // same roundings: bit-identical).
 struct LnBranch {
@@ -787,7 +787,7 @@ extern "C" int sm_layernorm_bwd(int x_dtype, int dy_dtype, int dx_dtype, int64_t
 }
 
 // sm_layernorm_bwd plus the branch copy dxb = bf16(bf16(dx) * row_scale[row / rpg] *
-// dropout keep / (1 - p)) (C = 192 or 384)
+// dropout keep * drop_scale(p)) (C = 192 or 384)
 extern "C" int sm_layernorm_bwd_branch(int x_dtype, int dy_dtype, int dx_dtype, int64_t M, int C, const void* dy,
                                        const void* x, const float* mean, const float* rstd, const float* gamma,
                                        void* dx, const void* dres, float* dgamma, float* dbeta, void* dxb,

@@ -117,7 +117,7 @@ def linear(x, w, bias=None, out_dtype=None, gelu=False, residual=None, round_bra
 def linear_dx(dy, w, out_dtype=None, residual=None, gelu_pre=None, drop_p=0.0, seed=0):
     """dx = dy @ w (+ residual);  dy [M,N], w [N,K].  gelu_pre: the input of a GELU (with
     dropout drop_p / seed on its output) that produced this Linear's input: returns the
-    gradient w.r.t. that pre-activation, dx * keep/(1-p) * GELU'(gelu_pre), in the
+    gradient w.r.t. that pre-activation, dx * keep * 256/(256-round(256p)) * GELU'(gelu_pre), in the
     epilogue (no dh round trip, no separate gelu_bwd pass)."""
     M, N = dy.shape
     K = w.shape[1]

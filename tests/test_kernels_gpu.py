@@ -252,6 +252,61 @@ def test_attention_dropout_exact_mask(dtype, D, L):
     assert rel_err(dqkv, dqkv_ref) < (1e-4 if dtype == torch.float32 else 3e-2)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_attention_argument_checks(dtype):
+    """sm_attn_fwd / sm_attn_bwd validate their arguments in one place, before any launch:
+    a head dim other than 32 / 64 and a workspace that is not 256-B aligned are refused
+    (-2, KernelError through the wrappers) and N = 0 succeeds as a no-op; in every case
+    the sentinel-filled output buffers stay untouched."""
+    from ssl_mae_amd import _lib
+    kk = KK()
+    N, L, H = 1, 33, 1
+    SENT = 7.0
+
+    def buffers(D):
+        qkv = rnd(N * L, 3 * H * D, dtype=dtype, seed=90 + D).to(DEV)
+        o = torch.full((N * L, H * D), SENT, dtype=dtype, device=DEV)
+        do = rnd(N * L, H * D, dtype=dtype, seed=91 + D).to(DEV)
+        lse = torch.full((N, H, L), SENT, dtype=torch.float32, device=DEV)
+        dqkv = torch.full_like(qkv, SENT)
+        nbytes = _lib.query("sm_attn_bwd_workspace_bytes", _lib.dt(qkv), N, L, H, D)
+        ws = torch.zeros(nbytes + 512, dtype=torch.uint8, device=DEV)
+        ws_ptr = (ws.data_ptr() + 255) // 256 * 256
+        return qkv, o, do, lse, dqkv, ws, ws_ptr
+
+    def fwd(n, D, qkv, o, lse):
+        return _lib.query("sm_attn_fwd", _lib.dt(qkv), n, L, H, D, _lib.ptr(qkv), _lib.ptr(o), _lib.ptr(lse),
+                          1.0 / math.sqrt(D), 0.0, 0, _lib.stream())
+
+    def bwd(n, D, qkv, o, do, lse, ws_ptr, dqkv):
+        return _lib.query("sm_attn_bwd", _lib.dt(qkv), n, L, H, D, _lib.ptr(qkv), _lib.ptr(o), _lib.ptr(do),
+                          _lib.ptr(lse), ws_ptr, _lib.ptr(dqkv), 1.0 / math.sqrt(D), 0.0, 0, _lib.stream())
+
+    def untouched(*ts):
+        torch.cuda.synchronize()
+        return all(bool((t == SENT).all()) for t in ts)
+
+    # head dim 48: refused by both entry points
+    qkv, o, do, lse, dqkv, ws, ws_ptr = buffers(48)
+    assert fwd(N, 48, qkv, o, lse) == -2
+    assert bwd(N, 48, qkv, o, do, lse, ws_ptr, dqkv) == -2
+    with pytest.raises(_lib.KernelError):
+        kk.attn_fwd(qkv, N, L, H, 48)
+    with pytest.raises(_lib.KernelError):
+        kk.attn_bwd(qkv, o, do, lse, N, L, H, 48)
+    assert untouched(o, lse, dqkv)
+    # a workspace pointer 16 B off its 256-B alignment
+    qkv, o, do, lse, dqkv, ws, ws_ptr = buffers(32)
+    with pytest.raises(_lib.KernelError, match="status -2"):
+        _lib.call("sm_attn_bwd", _lib.dt(qkv), N, L, H, 32, _lib.ptr(qkv), _lib.ptr(o), _lib.ptr(do), _lib.ptr(lse),
+                  ws_ptr + 16, _lib.ptr(dqkv), 1.0 / math.sqrt(32), 0.0, 0, _lib.stream())
+    assert untouched(dqkv)
+    # N = 0: success, nothing written
+    assert fwd(0, 32, qkv, o, lse) == 0
+    assert bwd(0, 32, qkv, o, do, lse, ws_ptr, dqkv) == 0
+    assert untouched(o, lse, dqkv) and not ws.any()
+
+
 # ------------------------------------------------------------------ LayerNorm
 @pytest.mark.parametrize("xd,yd", [(torch.float32, torch.float32), (torch.bfloat16, torch.bfloat16),
                                    (torch.float32, torch.bfloat16)])
