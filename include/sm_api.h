@@ -521,6 +521,57 @@ int sm_adamw(float* p, const float* g, float* m, float* v, void* bf16_shadow, in
              float b1, float b2, float eps, float wd, const int* found_inf, int64_t* step,
              int advance_step, hipStream_t st);
 
+/* ---- temporal SSL pretraining (src/train_ssl.py; csrc/temporal.hip).  No atomics: every
+ * reduction has a fixed partition and order, results are bitwise reproducible.
+ *
+ * sm_mfm_loss_fwd: the masked-frame objective (train_ssl.py:26-34, :215-220) over the N rows idx
+ * (int32, ascending, each in [0, R)) of pred [R][D] (fp32 or bf16) and teacher [R][D] (fp32), both
+ * contiguous.  With s_i = pred_i / max(|pred_i|, 1e-12) and u_i the same of the teacher row:
+ *   mfm     = 2 - (2 / N) sum_i s_i . u_i
+ *   sigma_c = sqrt(biased var_i(s_ic) + eps),  var = mean_c max(0, target_std - sigma_c)
+ *   out[3]  = mfm, var, w_mfm mfm + w_var var
+ * (the reference normalises a second time inside cosine_loss: the identity up to rounding).
+ * stats (fp32, 3 N + 2 D elements) receives what the backward reuses: per masked row the two
+ * inverse norms and the cosine, per column the mean and the hinge's factor.  Workspace
+ * sm_mfm_loss_workspace_bytes (8-byte aligned; -4 if short).  Row dot products are fp32 fmas in
+ * a fixed lane ownership, sums over rows / columns fp64.
+ * sm_mfm_loss_bwd: dpred [R][D] (fp32 or bf16) = grad_out[0] (device scalar) x d out[2] / d pred;
+ * rows not in idx are written as exact zeros.
+ * Both have a 16-byte form (D a multiple of 16 bytes of the pred dtype, bases 16-byte aligned)
+ * and a scalar form with the same element ownership: same bits.  -2 on a bad shape (N > R,
+ * N > 32 * 65535), dtype or null pointer; nothing is launched then. */
+int64_t sm_mfm_loss_workspace_bytes(int N, int D);
+int sm_mfm_loss_fwd(int pred_dtype, const void* pred, const float* teacher, const int32_t* idx, int R, int N,
+                    int D, float w_mfm, float w_var, float target_std, float eps, float* out, float* stats,
+                    void* ws, int64_t ws_bytes, hipStream_t st);
+int sm_mfm_loss_bwd(int pred_dtype, int dpred_dtype, const void* pred, const float* teacher, const int32_t* idx,
+                    int R, int N, int D, const float* stats, const float* grad_out, float w_mfm, float w_var,
+                    void* dpred, hipStream_t st);
+/* update_ema (train_ssl.py:36-39) over flat fp32 buffers: dst = m dst + one_minus_m src, the
+ * product rounded and the sum one fma; one launch.  The caller passes fp32(m) and
+ * fp32(1.0 - m), the difference formed in double, as torch rounds the two scalars. */
+int sm_ema_update(float* dst, const float* src, int64_t n, float m, float one_minus_m, hipStream_t st);
+/* torch.nn.utils.clip_grad_norm_ (train_ssl.py:258-259) over the element ranges
+ * [starts[i], ends[i]) of grad (HOST arrays): norm_out[0] = the L2 norm of the ranges' elements
+ * (squares added in fp64: per 8192-element chunk of a range, then over the chunks in order),
+ * then grad *= coef, coef = min(1, max_norm / (norm + 1e-6)) formed in fp32 on the device (no
+ * host synchronise; coef == 1 writes nothing).  A non-finite norm leaves non-finite values in
+ * grad, as torch with error_if_nonfinite=False.  Workspace sm_grad_clip_workspace_bytes (-1 on
+ * a bad range), 8-byte aligned. */
+int64_t sm_grad_clip_workspace_bytes(const int64_t* starts, const int64_t* ends, int nranges);
+int sm_grad_clip(float* grad, const int64_t* starts, const int64_t* ends, int nranges, float max_norm,
+                 float* norm_out, void* ws, int64_t ws_bytes, hipStream_t st);
+/* nn.TransformerEncoderLayer's ReLU + dropout on [n / ncols][ncols] (fp32 or bf16, ncols % 8 == 0,
+ * 16-byte aligned): y = max(x, 0) keep(row, col) drop_scale16(p), the mask csrc/common.h's counter
+ * hash of (seed, row, col) with the 16-bit threshold round(65536 p) (keep rate 0.899994 at
+ * p = 0.1, kept values scaled by its inverse); drop_p == 0 is ReLU bit for bit (NaN stays NaN).
+ * Backward: dx = dy keep drop_scale16(p) where ref > 0, the mask regenerated from the seed; ref is
+ * the forward's x or its y. */
+int sm_relu_dropout_fwd(int dtype, int64_t n, int ncols, const void* x, void* y, float drop_p, uint64_t seed,
+                        hipStream_t st);
+int sm_relu_dropout_bwd(int dtype, int64_t n, int ncols, const void* ref, const void* dy, void* dx, float drop_p,
+                        uint64_t seed, hipStream_t st);
+
 /* ---- federated averaging (src/federated/fed_loop.py:14-62 fedavg_aggregate).
  * out[i] = sum_j client_bufs[j][i] * weights[j], accumulated from +0 in client order
  * with the product and the sum rounded separately (fed_loop.py:46-49, weights[j] =

@@ -268,6 +268,20 @@ SM_DEV bool drop_keep(uint32_t s32, uint64_t row, uint32_t col, uint32_t thr) {
   return drop_keep_bits(drop_hash(drop_rowbase(s32, row), col), col, thr);
 }
 
+// The same rule with a 16-bit threshold, one hash per 2 columns (csrc/temporal.hip's ReLU +
+// dropout, which follows nn.Dropout(0.1) rather than the SDPA convention): keep = half-word >=
+// round(65536 p), kept values scaled by 65536 / (65536 - thr), again the inverse of the quantised
+// keep rate.  At p = 0.1 the keep rate is 58982 / 65536 = 0.899994 (8 bits: 230 / 256 = 0.8984).
+SM_DEV uint32_t drop_hash16(uint32_t rowbase, uint32_t col) { return fmix32(rowbase + (col >> 1) * 0x7FEB352Du); }
+SM_DEV uint32_t drop_thr16(float p) { return (uint32_t)(p * 65536.f + 0.5f); }
+SM_DEV float drop_scale16(float p) {
+  const uint32_t t = drop_thr16(p);
+  return t >= 65536u ? 0.f : 65536.f / (float)(65536u - t);
+}
+SM_DEV bool drop_keep_bits16(uint32_t h, uint32_t col, uint32_t thr) {
+  return ((h >> ((col & 1) * 16)) & 0xFFFFu) >= thr;
+}
+
 // Reduce partial slabs part[nb][ncols] over nb.  Block = 32 columns x 8 row groups;
 // fp64 accumulation, fixed order (deterministic).  Writes fp64 (outd) and/or
 // fp32 (outf, optionally accumulating).

@@ -164,6 +164,16 @@ _SIGS = {
     "sm_mae_reconstruct": (_c_i32, [_c_i32, _c_p, _c_p] + [_c_i64] * 5 + [_c_p] + [_c_i32] * 4 + [_c_p, _c_p]
                            + [_c_i32] * 3 + [_c_p] * 4),
     "sm_recon_clip_metrics": (_c_i32, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p]),
+    "sm_mfm_loss_workspace_bytes": (_c_i64, [_c_i32, _c_i32]),
+    "sm_mfm_loss_fwd": (_c_i32, [_c_i32, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32] + [_c_f32] * 4
+                        + [_c_p, _c_p, _c_p, _c_i64, _c_p]),
+    "sm_mfm_loss_bwd": (_c_i32, [_c_i32, _c_i32, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_f32, _c_f32,
+                                 _c_p, _c_p]),
+    "sm_ema_update": (_c_i32, [_c_p, _c_p, _c_i64, _c_f32, _c_f32, _c_p]),
+    "sm_grad_clip_workspace_bytes": (_c_i64, [_c_p, _c_p, _c_i32]),
+    "sm_grad_clip": (_c_i32, [_c_p, _c_p, _c_p, _c_i32, _c_f32, _c_p, _c_p, _c_i64, _c_p]),
+    "sm_relu_dropout_fwd": (_c_i32, [_c_i32, _c_i64, _c_i32, _c_p, _c_p, _c_f32, _c_u64, _c_p]),
+    "sm_relu_dropout_bwd": (_c_i32, [_c_i32, _c_i64, _c_i32, _c_p, _c_p, _c_p, _c_f32, _c_u64, _c_p]),
 }
 
 _lib = None

@@ -21,8 +21,10 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", CSRC, "-I
          "-Wno-unused-result", "-munsafe-fp-atomics"]
 # Per-source extra flags.  fed.hip reproduces the reference's separately rounded
 # multiply and add bit for bit; hipcc's default -ffp-contract=fast ignores
-# `#pragma clang fp contract`, so contraction is switched off for that file.
-FILE_FLAGS = {"fed.hip": ["-ffp-contract=off"], "attention.hip": ["-fno-slp-vectorize"], "gemm.hip": ["-fno-slp-vectorize"]}
+# `#pragma clang fp contract`, so contraction is switched off for that file.  temporal.hip's
+# 16-byte and scalar forms must round alike: its fmas are explicit, nothing else may fuse.
+FILE_FLAGS = {"fed.hip": ["-ffp-contract=off"], "temporal.hip": ["-ffp-contract=off"],
+              "attention.hip": ["-fno-slp-vectorize"], "gemm.hip": ["-fno-slp-vectorize"]}
 
 
 def _sources():

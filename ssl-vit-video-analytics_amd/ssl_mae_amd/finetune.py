@@ -138,11 +138,16 @@ def load_pretrained_ssl(model, ckpt_path):
     (train_ssl_mae.py:190-194, `encoder_ep{N}.pth`), which the reference's loader
     silently skips; such a file is loaded as the backbone state directly.  A full
     MAE state (`encoder.`-prefixed, optionally under "model") loads as in the
-    reference."""
+    reference.  A temporal-SSL checkpoint (temporal_ssl.py / train_ssl.py:355-361,
+    `ssl_ep{N}.pth` with keys epoch / student / ema / opt) gives its `student`'s
+    `encoder.*`; the reference's own loader looks for `encoder.` at the top level of such
+    a file and finds nothing."""
     if ckpt_path is None or not os.path.isfile(ckpt_path):
         print("[INFO] No SSL checkpoint loaded")
         return False
     ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
+    if isinstance(ckpt.get("student"), dict) and "model" not in ckpt:
+        ckpt = ckpt["student"]
     state = ckpt.get("model", ckpt)
     backbone_state = {k[len("encoder."):]: v for k, v in state.items() if k.startswith("encoder.")}
     if not backbone_state:

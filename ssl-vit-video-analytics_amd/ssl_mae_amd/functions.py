@@ -405,7 +405,13 @@ class BlockFn(torch.autograd.Function):
         x2 = K.linear(o, W(wproj, mode), bproj.detach(), out_dtype=x.dtype, residual=x, round_branch=rb,
                       drop_p=st.drop1, seed=st.seed1, row_scale=st.dp1, rows_per_group=L)
         ln2, mu2, rs2 = K.layernorm(x2, ln2w.detach(), ln2b.detach(), out_dtype=act, eps=st.eps)
-        h, hpre = K.linear(ln2, W(w1, mode), b1.detach(), gelu=True, drop_p=st.drop_ff, seed=st.seed_ff)
+        if getattr(st, "relu", False):
+            # nn.TransformerEncoderLayer's default activation (train_ssl.py:111-117): the GEMM's
+            # epilogues stay as they are, ReLU + dropout is one elementwise pass; the backward
+            # needs only its output, kept in hpre's slot
+            h = hpre = K.relu_dropout_fwd(K.linear(ln2, W(w1, mode), b1.detach()), st.drop_ff, st.seed_ff)
+        else:
+            h, hpre = K.linear(ln2, W(w1, mode), b1.detach(), gelu=True, drop_p=st.drop_ff, seed=st.seed_ff)
         del ln2
         out = K.linear(h, W(w2, mode), b2.detach(), out_dtype=x.dtype, residual=x2, round_branch=rb,
                        drop_p=st.drop2, seed=st.seed2, row_scale=st.dp2, rows_per_group=L)
@@ -437,7 +443,10 @@ class BlockFn(torch.autograd.Function):
                 db = K.dropout_bwd(db, st.drop2, st.seed2, st.dp2, L)
         # dL/dhpre straight from the fc2 data-gradient GEMM's epilogue (keep mask and
         # GELU' applied there: no dh round trip, no gelu_bwd pass)
-        if rb and db.shape[1] <= 256:
+        if getattr(st, "relu", False):   # hpre holds h = dropout(ReLU(pre)): positive where kept
+            K.linear_dw_bias(db, hpre, G(w2), G(b2))
+            dhpre = K.relu_dropout_bwd(hpre, K.linear_dx(db, W(w2, mode)), st.drop_ff, st.seed_ff)
+        elif rb and db.shape[1] <= 256:
             # one-m-tile fc2 weight gradient: dropout(GELU(hpre)) formed in its operand loads
             K.linear_dw_bias(db, hpre, G(w2), G(b2), gelu=(st.drop_ff, st.seed_ff))
             dhpre = K.linear_dx(db, W(w2, mode), gelu_pre=hpre, drop_p=st.drop_ff, seed=st.seed_ff)

@@ -1209,3 +1209,121 @@ def recon_clip_metrics(token_err, mask_u8):
     out = torch.empty((B, 4), dtype=torch.float32, device=token_err.device)
     call("sm_recon_clip_metrics", ptr(token_err), ptr(mask_u8), B, T, L, ptr(out), stream())
     return out
+
+
+# ------------------------------------------------------------------ temporal SSL pretraining
+def _mfm_args(pred, teacher, idx, what):
+    """Shapes and dtypes only.  The CALLER guarantees that idx is strictly ascending with every
+    entry in [0, R): it lives on the device and is not read back here.  The backward finds a row
+    by binary search, so an unsorted or repeated list gives zero or wrong gradient rows although
+    the forward looks right (temporal_ssl builds it as nonzero() of the host mask: ascending)."""
+    _chk(pred, teacher, idx)
+    if pred.dim() != 2 or not pred.is_contiguous() or pred.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.KernelError(f"{what}: pred must be a contiguous fp32 or bf16 matrix")
+    R, D = pred.shape
+    if teacher.dtype != torch.float32 or teacher.shape != pred.shape or not teacher.is_contiguous():
+        raise _lib.KernelError(f"{what}: teacher must be contiguous fp32 [{R},{D}]")
+    if idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous():
+        raise _lib.KernelError(f"{what}: idx must be a contiguous int32 vector")
+    N = idx.numel()
+    if not 1 <= N <= R:
+        raise _lib.KernelError(f"{what}: {N} masked rows of a [{R},{D}] matrix")
+    if pred.device != teacher.device or pred.device != idx.device:
+        raise _lib.KernelError(f"{what}: pred, teacher and idx must be on one device")
+    return R, N, D
+
+
+def mfm_loss_fwd(pred, teacher, idx, w_mfm=1.0, w_var=1.0, target_std=1.0, eps=1e-4):
+    """pred [R,D] (fp32 / bf16), teacher fp32 [R,D], idx int32 [N] strictly ascending (the
+    caller's guarantee, see _mfm_args) ->
+    (out fp32 [3] = mfm, var, w_mfm mfm + w_var var; stats fp32 [3N + 2D] for mfm_loss_bwd)."""
+    R, N, D = _mfm_args(pred, teacher, idx, "mfm_loss_fwd")
+    out = torch.empty(3, dtype=torch.float32, device=pred.device)
+    stats = torch.empty(3 * N + 2 * D, dtype=torch.float32, device=pred.device)
+    nbytes = query("sm_mfm_loss_workspace_bytes", N, D)
+    ws = _ws(nbytes, pred.device)
+    call("sm_mfm_loss_fwd", dt(pred), ptr(pred), ptr(teacher), ptr(idx), R, N, D, float(w_mfm), float(w_var),
+         float(target_std), float(eps), ptr(out), ptr(stats), ptr(ws), nbytes, stream())
+    return out, stats
+
+
+def mfm_loss_bwd(pred, teacher, idx, stats, grad_out, w_mfm=1.0, w_var=1.0, out_dtype=None):
+    """-> dpred [R,D] (out_dtype, default pred's) = grad_out (device scalar) x d total / d pred;
+    rows outside idx are exact zeros."""
+    R, N, D = _mfm_args(pred, teacher, idx, "mfm_loss_bwd")
+    _chk(stats, grad_out)
+    if stats.dtype != torch.float32 or stats.numel() != 3 * N + 2 * D or not stats.is_contiguous():
+        raise _lib.KernelError("mfm_loss_bwd: stats must be the forward's fp32 [3N + 2D] buffer")
+    if grad_out.dtype != torch.float32 or grad_out.numel() != 1:
+        raise _lib.KernelError("mfm_loss_bwd: grad_out must be one fp32 value on the device")
+    dpred = torch.empty((R, D), dtype=out_dtype or pred.dtype, device=pred.device)
+    call("sm_mfm_loss_bwd", dt(pred), dt(dpred), ptr(pred), ptr(teacher), ptr(idx), R, N, D, ptr(stats),
+         ptr(grad_out), float(w_mfm), float(w_var), ptr(dpred), stream())
+    return dpred
+
+
+def ema_update(dst, src, m):
+    """dst = m dst + (1 - m) src over contiguous fp32 buffers of one length, in place."""
+    _chk(dst, src)
+    if dst.dtype != torch.float32 or src.dtype != torch.float32 or dst.numel() != src.numel() \
+            or not dst.is_contiguous() or not src.is_contiguous() or dst.device != src.device:
+        raise _lib.KernelError("ema_update takes two contiguous fp32 buffers of one length on one device")
+    m = float(m)
+    call("sm_ema_update", ptr(dst), ptr(src), dst.numel(), m, 1.0 - m, stream())    # each rounded to fp32 by ctypes
+    return dst
+
+
+def grad_clip(grad, ranges, max_norm, norm_out=None):
+    """clip_grad_norm_ over the element ranges [(start, end), ...] of the flat fp32 gradient
+    buffer, in place; -> the total norm as a device tensor (no host synchronise)."""
+    import ctypes
+    _chk(grad, norm_out)
+    if grad.dtype != torch.float32 or grad.dim() != 1 or not grad.is_contiguous():
+        raise _lib.KernelError("grad_clip takes a contiguous flat fp32 gradient buffer")
+    n = len(ranges)
+    prev = 0
+    for s, e in ranges:
+        if not prev <= s <= e <= grad.numel():
+            raise _lib.KernelError(f"grad_clip: range [{s},{e}) is out of order or outside the {grad.numel()} elements")
+        prev = e
+    if norm_out is None:
+        norm_out = torch.empty(1, dtype=torch.float32, device=grad.device)
+    elif norm_out.dtype != torch.float32 or norm_out.numel() != 1 or norm_out.device != grad.device:
+        raise _lib.KernelError("grad_clip: norm_out must be one fp32 value on the gradient's device")
+    starts = (ctypes.c_int64 * max(n, 1))(*[int(s) for s, _ in ranges])
+    ends = (ctypes.c_int64 * max(n, 1))(*[int(e) for _, e in ranges])
+    sp, ep = ctypes.cast(starts, ctypes.c_void_p), ctypes.cast(ends, ctypes.c_void_p)
+    nbytes = query("sm_grad_clip_workspace_bytes", sp, ep, n)
+    if nbytes < 0:
+        raise _lib.KernelError("grad_clip: bad ranges")
+    ws = _ws(nbytes, grad.device)
+    call("sm_grad_clip", ptr(grad), sp, ep, n, float(max_norm), ptr(norm_out), ptr(ws), nbytes, stream())
+    return norm_out
+
+
+def _relu_dropout_args(x, what):
+    _chk(x)
+    if x.dim() < 1 or not x.is_contiguous() or x.dtype not in (torch.float32, torch.bfloat16) \
+            or x.shape[-1] % 8 or x.data_ptr() % 16:
+        raise _lib.KernelError(f"{what} takes contiguous 16-byte aligned fp32 / bf16 rows of a multiple of 8 columns")
+
+
+def relu_dropout_fwd(x, drop_p=0.0, seed=0):
+    """y = relu(x) * keep * drop_scale(p), the mask a function of (seed, row, column)."""
+    _relu_dropout_args(x, "relu_dropout_fwd")
+    y = torch.empty_like(x)
+    call("sm_relu_dropout_fwd", dt(x), x.numel(), x.shape[-1], ptr(x), ptr(y), float(drop_p),
+         int(seed) & ((1 << 64) - 1), stream())
+    return y
+
+
+def relu_dropout_bwd(ref, dy, drop_p=0.0, seed=0):
+    """dx = dy * keep * drop_scale(p) where ref > 0 (ref: the forward's input or output)."""
+    _relu_dropout_args(ref, "relu_dropout_bwd")
+    _relu_dropout_args(dy, "relu_dropout_bwd")
+    if dy.shape != ref.shape or dy.dtype != ref.dtype or dy.device != ref.device:
+        raise _lib.KernelError("relu_dropout_bwd: dy must match ref")
+    dx = torch.empty_like(dy)
+    call("sm_relu_dropout_bwd", dt(ref), ref.numel(), ref.shape[-1], ptr(ref), ptr(dy), ptr(dx), float(drop_p),
+         int(seed) & ((1 << 64) - 1), stream())
+    return dx

@@ -1448,6 +1448,91 @@ def recon_clip_metrics(token_err, mask_u8):
     return torch.ops.ssl_mae.recon_clip_metrics(token_err, mask_u8)
 
 
+# ============================================================================ temporal SSL pretraining
+@_op("mfm_loss_fwd", "(Tensor pred, Tensor teacher, Tensor idx, float w_mfm, float w_var, float target_std, float eps) "
+                     "-> (Tensor, Tensor)")
+def _mfm_loss_fwd(pred, teacher, idx, w_mfm, w_var, target_std, eps):
+    return _K.mfm_loss_fwd(pred, teacher, idx, w_mfm, w_var, target_std, eps)
+
+
+@_mfm_loss_fwd.register_fake
+def _(pred, teacher, idx, w_mfm, w_var, target_std, eps):
+    return (pred.new_empty((3,), dtype=torch.float32),
+            pred.new_empty((3 * idx.shape[0] + 2 * pred.shape[1],), dtype=torch.float32))
+
+
+def mfm_loss_fwd(pred, teacher, idx, w_mfm=1.0, w_var=1.0, target_std=1.0, eps=1e-4):
+    return torch.ops.ssl_mae.mfm_loss_fwd(pred, teacher, idx, float(w_mfm), float(w_var), float(target_std), float(eps))
+
+
+@_op("mfm_loss_bwd", "(Tensor pred, Tensor teacher, Tensor idx, Tensor stats, Tensor grad_out, float w_mfm, "
+                     "float w_var, ScalarType? out_dtype) -> Tensor")
+def _mfm_loss_bwd(pred, teacher, idx, stats, grad_out, w_mfm, w_var, out_dtype):
+    return _K.mfm_loss_bwd(pred, teacher, idx, stats, grad_out, w_mfm, w_var, out_dtype)
+
+
+_mfm_loss_bwd.register_fake(lambda pred, teacher, idx, stats, grad_out, w_mfm, w_var, out_dtype: pred.new_empty(
+    pred.shape, dtype=out_dtype or pred.dtype))
+
+
+def mfm_loss_bwd(pred, teacher, idx, stats, grad_out, w_mfm=1.0, w_var=1.0, out_dtype=None):
+    return torch.ops.ssl_mae.mfm_loss_bwd(pred, teacher, idx, stats, grad_out, float(w_mfm), float(w_var), out_dtype)
+
+
+@_op("ema_update", "(Tensor(a!) dst, Tensor src, float m) -> ()", ("dst",))
+def _ema_update(dst, src, m):
+    _K.ema_update(dst, src, m)
+
+
+_ema_update.register_fake(_none)
+
+
+def ema_update(dst, src, m):
+    torch.ops.ssl_mae.ema_update(dst, src, float(m))
+    return dst
+
+
+@_op("grad_clip", "(Tensor(a!) grad, int[] starts, int[] ends, float max_norm, Tensor(b!) norm_out) -> ()",
+     ("grad", "norm_out"))
+def _grad_clip(grad, starts, ends, max_norm, norm_out):
+    _K.grad_clip(grad, list(zip(starts, ends)), max_norm, norm_out)
+
+
+_grad_clip.register_fake(_none)
+
+
+def grad_clip(grad, ranges, max_norm, norm_out=None):
+    if norm_out is None:
+        norm_out = torch.empty(1, dtype=torch.float32, device=grad.device)
+    torch.ops.ssl_mae.grad_clip(grad, [int(s) for s, _ in ranges], [int(e) for _, e in ranges], float(max_norm),
+                                norm_out)
+    return norm_out
+
+
+@_op("relu_dropout_fwd", "(Tensor x, float drop_p, int seed) -> Tensor")
+def _relu_dropout_fwd(x, drop_p, seed):
+    return _K.relu_dropout_fwd(x, drop_p, _u64(seed))
+
+
+_relu_dropout_fwd.register_fake(lambda x, drop_p, seed: torch.empty_like(x))
+
+
+def relu_dropout_fwd(x, drop_p=0.0, seed=0):
+    return torch.ops.ssl_mae.relu_dropout_fwd(x, float(drop_p), _s64(seed))
+
+
+@_op("relu_dropout_bwd", "(Tensor ref, Tensor dy, float drop_p, int seed) -> Tensor")
+def _relu_dropout_bwd(ref, dy, drop_p, seed):
+    return _K.relu_dropout_bwd(ref, dy, drop_p, _u64(seed))
+
+
+_relu_dropout_bwd.register_fake(lambda ref, dy, drop_p, seed: torch.empty_like(dy))
+
+
+def relu_dropout_bwd(ref, dy, drop_p=0.0, seed=0):
+    return torch.ops.ssl_mae.relu_dropout_bwd(ref, dy, float(drop_p), _s64(seed))
+
+
 def registered_ops():
     """Names of every ssl_mae operator registered by this module."""
     return sorted(n for n in dir(torch.ops.ssl_mae) if not n.startswith("_") and
