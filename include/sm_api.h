@@ -595,6 +595,27 @@ int sm_fedavg_counters_max(int num_clients, const int64_t* const* client_counter
 int sm_frames_normalize(const uint8_t* frames, const uint8_t* valid, int B, int T, int H, int W, const float* mean3,
                         const float* std3, int bgr_swap, float* out, hipStream_t st);
 
+/* Resize + flip + normalise a batch of decoded clips that each keep their own frame size
+ * (src/datasets/mae_dataset.py:84-90 u8 / 255 -> F.interpolate(bilinear, align_corners=False)
+ * -> clip-level horizontal flip -> Normalize), one launch, no workspace, no host sync.
+ * packed uint8: clip b is [T][Hs_b][Ws_b][3] (RGB, HWC) starting at byte desc[b][0];
+ * desc int64 [B][4] (DEVICE) = {byte offset, Hs, Ws, flags}, flags bit 0 = flip horizontally,
+ * bit 1 = invalid clip.  out fp32 [B][3][T][Ho][Wo], Ho, Wo <= 4096.  A clip is written as
+ * zeros when it is flagged invalid, when Hs or Ws is outside [1, 8192] or when its byte range
+ * leaves [0, packed_bytes); nothing outside `packed` is read.  Per axis (n_in source, n_out
+ * output samples, output index d): n_in == n_out takes sample d; otherwise scale = fp32(n_in) /
+ * fp32(n_out), src = max(fma(scale, d + 0.5, -0.5), 0), i0 = min((int)src, n_in - 1),
+ * l1 = clamp(src - i0, 0, 1), i1 = i0 + (i0 < n_in - 1), l0 = 1 - l1.  With p = fp32(u) / 255:
+ * r = l0y (l0x p00 + l1x p01) + l1y (l0x p10 + l1x p11), every product and sum rounded on its
+ * own; a flipped clip writes column x's r to column Wo-1-x; out[c] = (r - mean[s]) / std[s],
+ * s = 2 - c when bgr_swap (source channel s).  A clip already at (Ho, Wo), not flipped, equals
+ * sm_frames_normalize bit for bit.  mean3 / std3 are HOST arrays of 3 floats.  Returns 0 (also
+ * for an empty output), -2 for a null pointer or a bad count (nothing launched), or the
+ * hipError_t of the launch. */
+int sm_frames_resize_normalize(const uint8_t* packed, const int64_t* desc, int64_t packed_bytes, int B, int T, int Ho,
+                               int Wo, const float* mean3, const float* std3, int bgr_swap, float* out,
+                               hipStream_t st);
+
 /* ---- box calibration (bench.py; csrc/calib.hip): `blocks` workgroups of 4 waves, each wave
  * `iters` x 8 v_mfma_f32_32x32x16_bf16 (shape 32) or the same FLOPs as 16
  * v_mfma_f32_16x16x32_bf16 (shape 16) on random register operands.  stamps [blocks][2] int64:

@@ -6,6 +6,11 @@
 * clip normalisation (sm_frames_normalize) at the bench batch: 256 clips x 8 frames
   x 224^2.  Algorithmic bytes = 3 (uint8 RGB read) + 12 (3 fp32 written) per pixel.
 
+* `aux_bench.py resize [--out profiles/resize.txt]`: clip resize + normalisation
+  (sm_frames_resize_normalize) at 256 clips x 8 frames, 112^2 -> 224^2 and 240x320 ->
+  112^2, next to sm_frames_normalize at the same output size, eager torch ops, the host
+  path on 16 threads and the 4.9 GB copy calibration (see `resize`).
+
 Prints one JSON line per kernel; run under rocprofv3 --kernel-trace --stats to
 cross-check the average launch durations."""
 import json
@@ -70,6 +75,133 @@ def main(k=4, iters=50):
                       "peak_gbs": 8000.0, "frac": round(gb / ms * 1e3 / 8000.0, 3)}))
 
 
+MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+def _rounds(fn, reps, rounds):
+    """[ms per call] over `rounds` event-timed windows of `reps` calls."""
+    out = []
+    for _ in range(rounds):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(reps):
+            fn()
+        e.record()
+        e.synchronize()
+        out.append(s.elapsed_time(e) / reps)
+    return out
+
+
+def _fmt(t):
+    import statistics
+    return f"{statistics.median(t):.3f} ms [{min(t):.3f} .. {max(t):.3f}]"
+
+
+def resize(out_path=None, B=256, T=8, reps=20, rounds=5, host_threads=16):
+    """sm_frames_resize_normalize at the bench batch for 112^2 -> 224^2 and 240x320 -> 112^2,
+    next to sm_frames_normalize at the same output size (same bytes written) in alternating
+    rounds, the same result from eager torch ops on the GPU, the host path
+    (mae_dataset.MAEVideoDataset(raw=False)'s per-frame arithmetic on `host_threads` threads,
+    decoding excluded) and the 4.9 GB copy calibration.  Algorithmic bytes of the resize:
+    every source byte once + 12 per output pixel."""
+    import statistics
+    import tempfile
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    import torch.nn.functional as Fn
+    from ssl_mae_amd.mae_dataset import MAEVideoDataset
+    dev = torch.device("cuda")
+    lines = [f"device: {torch.cuda.get_device_name(0)}; B={B} T={T}; {rounds} rounds of {reps} launches, "
+             "median [min .. max]"]
+    mean_t = torch.tensor(MEAN, device=dev).view(1, 3, 1, 1)
+    std_t = torch.tensor(STD, device=dev).view(1, 3, 1, 1)
+    for hs, ws, S in ((112, 112, 224), (240, 320, 112)):
+        src = torch.randint(0, 256, (B, T, hs, ws, 3), dtype=torch.uint8, device=dev)
+        desc = torch.tensor([[b * T * hs * ws * 3, hs, ws, b & 1] for b in range(B)], device=dev)   # every other clip flipped
+        same = torch.randint(0, 256, (B, T, S, S, 3), dtype=torch.uint8, device=dev)
+        out = torch.empty((B, 3, T, S, S), dtype=torch.float32, device=dev)
+        out2 = torch.empty_like(out)
+        packed = src.view(-1)
+
+        def k_resize():
+            K.frames_resize_normalize(packed, desc, T, (S, S), MEAN, STD, False, out)
+
+        def k_norm():
+            K.frames_normalize(same, MEAN, STD, False, None, out2)
+
+        def eager():
+            x = src.view(B * T, hs, ws, 3).permute(0, 3, 1, 2).float().div_(255.0)
+            x = Fn.interpolate(x, size=(S, S), mode="bilinear", align_corners=False)
+            x = torch.where((desc[:, 3] & 1).bool().repeat_interleave(T).view(-1, 1, 1, 1), x.flip(3), x)
+            x = (x - mean_t) / std_t
+            return x.view(B, T, 3, S, S).permute(0, 2, 1, 3, 4).contiguous()
+
+        for fn in (k_resize, k_norm, eager):            # warm-up: code objects, allocator
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        diff = float((eager() - out).abs().max())
+        tr, tn = [], []
+        for _ in range(rounds):                         # alternate the two kernels
+            tr += _rounds(k_resize, reps, 1)
+            tn += _rounds(k_norm, reps, 1)
+        te = _rounds(eager, 3, rounds)
+        gb_r = (B * T * hs * ws * 3 + out.numel() * 4) / 1e9
+        gb_n = (same.numel() + out.numel() * 4) / 1e9
+        mr, mn = statistics.median(tr), statistics.median(tn)
+        lines.append(f"{hs}x{ws} -> {S}x{S}:")
+        lines.append(f"  sm_frames_resize_normalize: {_fmt(tr)}  {gb_r:.3f} GB per launch  {gb_r / mr * 1e3:.0f} GB/s")
+        lines.append(f"  sm_frames_normalize at {S}x{S}: {_fmt(tn)}  {gb_n:.3f} GB per launch  {gb_n / mn * 1e3:.0f} GB/s"
+                     f"  (resize / normalize time: {mr / mn:.2f})")
+        lines.append(f"  eager torch ops on the GPU (float, div, interpolate, flip, normalize, permute): {_fmt(te)}  "
+                     f"{statistics.median(te) / mr:.1f}x the kernel; max |eager - kernel| = {diff:.2e}")
+        # host path: the reference item's arithmetic per frame, one torch thread per worker
+        frames_np = src.cpu().numpy()
+        with tempfile.NamedTemporaryFile("w", suffix=".txt") as f:
+            ds = MAEVideoDataset(f.name, image_size=S, clip_len=T)
+
+        def host_clip(b):
+            flip = bool(b & 1)
+            imgs = []
+            for t in range(T):
+                x = ds._resize_tensor(frames_np[b, t])
+                if flip:
+                    x = torch.flip(x, dims=[2])
+                imgs.append((x - ds.mean) / ds.std)
+            return torch.stack(imgs, dim=0).permute(1, 0, 2, 3).contiguous()
+
+        nt = torch.get_num_threads()
+        torch.set_num_threads(1)
+        th = []
+        with ThreadPoolExecutor(host_threads) as ex:
+            list(ex.map(host_clip, range(min(B, 2 * host_threads))))          # warm-up
+            for _ in range(3):
+                t0 = time.perf_counter()
+                list(ex.map(host_clip, range(B)))
+                th.append((time.perf_counter() - t0) * 1e3)
+        torch.set_num_threads(nt)
+        lines.append(f"  host path, {host_threads} threads (resize + flip + normalize of {B * T} decoded frames): "
+                     f"{_fmt(th)}  {statistics.median(th) / mr:.0f}x the kernel")
+        del src, same, out, out2, packed
+        torch.cuda.empty_cache()
+    n = int(4.9e9) // 4
+    a, b = torch.empty(n, device=dev), torch.empty(n, device=dev)
+    b.copy_(a)
+    torch.cuda.synchronize()
+    tc = _rounds(lambda: b.copy_(a), 5, rounds)
+    lines.append(f"copy calibration (4.9 GB device-to-device, read + write): {_fmt(tc)}  "
+                 f"{2 * n * 4 / statistics.median(tc) / 1e6:.0f} GB/s")
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+
+
 if __name__ == "__main__":
-    main()
-    frames()
+    if len(sys.argv) > 1 and sys.argv[1] == "resize":
+        resize(sys.argv[3] if len(sys.argv) > 3 and sys.argv[2] == "--out" else None)
+    else:
+        main()
+        frames()

@@ -23,7 +23,9 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", CSRC, "-I
 # multiply and add bit for bit; hipcc's default -ffp-contract=fast ignores
 # `#pragma clang fp contract`, so contraction is switched off for that file.  temporal.hip's
 # 16-byte and scalar forms must round alike: its fmas are explicit, nothing else may fuse.
+# resize.hip's interpolation is matched bit for bit by a host mirror: one explicit fma, no other.
 FILE_FLAGS = {"fed.hip": ["-ffp-contract=off"], "temporal.hip": ["-ffp-contract=off"],
+              "resize.hip": ["-ffp-contract=off"],
               "attention.hip": ["-fno-slp-vectorize"], "gemm.hip": ["-fno-slp-vectorize"]}
 
 

@@ -15,6 +15,19 @@ empty directory.  What changes is where the per-pixel work runs:
   * transform=callable: the reference's behaviour verbatim (the callable runs per
     frame, then img[[2,1,0]] on tensors, stack, permute) — user code, on the host.
 
+Frames that are not already `image_size` (a 112² frame store feeding a 224² model, a
+dataset kept at its native 240x320) take `collate_raw` + `ClipResizer` instead of
+`collate_frames` + `ClipNormalizer`: the batch is packed into one flat uint8 buffer with
+a descriptor row {byte offset, Hs, Ws, flags} per clip, and sm_frames_resize_normalize
+resizes (bilinear, align_corners=False, the rule of src/datasets/mae_dataset.py:84-90),
+flips and normalises every clip in one launch.  A clip already at `image_size` comes out
+bit-identical to the ClipNormalizer path, so the drivers use this path for every split.
+Deviation: the reference's supervised loaders resize with cv2.resize
+(src/datasets/transforms.py:9-15), whose bilinear filter works in fixed-point uint8
+arithmetic.  OpenCV is not available to pin that arithmetic against, so every loader here
+gets the F.interpolate rule; the difference (cv2 rounds the interpolated value back to
+uint8) has not been measured.
+
 get_tube_mask (mae_loader.py:80-90) keeps the reference's signature and RNG stream:
 the per-sample noise is drawn on the host from torch's global CPU generator exactly
 as the reference draws it (B calls of torch.rand(L) == torch.rand(B, L)); the
@@ -69,6 +82,25 @@ class LazyVideoMAEDataset(torch.utils.data.Dataset):
         except Exception:
             return Image.new("RGB", (self.image_size, self.image_size), (0, 0, 0))
 
+    def _load_raw(self, video_dir, paths):
+        """The transform=None clip: uint8 [T,Hs,Ws,3] at the frames' own size.  An unreadable
+        frame is black at that size (image_size when no frame of the clip can be read), so it
+        resizes to exactly the normalised black frame the reference substitutes."""
+        from PIL import Image
+        frames = []
+        for p in paths:
+            try:
+                frames.append(np.asarray(Image.open(p).convert("RGB"), dtype=np.uint8))
+            except Exception:
+                frames.append(None)
+        shapes = sorted({f.shape for f in frames if f is not None})
+        if len(shapes) > 1:
+            raise ValueError(f"frames of {video_dir} differ in size ({', '.join(f'{h}x{w}' for h, w, _ in shapes)}): "
+                             "one clip must have one frame size")
+        shape = shapes[0] if shapes else (self.image_size, self.image_size, 3)
+        black = np.zeros(shape, dtype=np.uint8)
+        return torch.from_numpy(np.stack([black if f is None else f for f in frames]))
+
     def _indices(self, total):
         window = self.clip_len * self.stride
         if total < window:
@@ -91,9 +123,10 @@ class LazyVideoMAEDataset(torch.utils.data.Dataset):
         names = sorted(f for f in os.listdir(video_dir) if f.endswith(".jpg"))
         if not names:
             return self._empty()
-        imgs = [self._load_frame(os.path.join(video_dir, names[i])) for i in self._indices(len(names))]
+        paths = [os.path.join(video_dir, names[i]) for i in self._indices(len(names))]
         if self.transform is None:
-            return torch.from_numpy(np.stack([np.asarray(im, dtype=np.uint8) for im in imgs])), True
+            return self._load_raw(video_dir, paths), True
+        imgs = [self._load_frame(p) for p in paths]
         clip = []
         for img in imgs:
             img = self.transform(img)
@@ -120,6 +153,74 @@ class ClipNormalizer:
         f = frames.to(self.device, non_blocking=True)
         v = None if valid is None else valid.to(self.device, non_blocking=True)
         return K.frames_normalize(f.contiguous(), self.mean, self.std, self.bgr_swap, v)
+
+
+FLAG_FLIP, FLAG_INVALID = 1, 2     # desc[b, 3] of sm_frames_resize_normalize
+MAX_SOURCE_SIDE = 8192
+
+
+def collate_raw(batch):
+    """DataLoader collate for clips that keep their own frame size.  Items are
+    (uint8 [T,Hs,Ws,3], valid) or (frames, valid, flip); returns (packed uint8 1-D, desc
+    int64 [B,4] = {byte offset, Hs, Ws, flags}).  An invalid item contributes no bytes."""
+    desc = torch.zeros(len(batch), 4, dtype=torch.int64)
+    parts, off, clip_len = [], 0, None
+    for b, item in enumerate(batch):
+        frames, valid = item[0], item[1]
+        flip = bool(item[2]) if len(item) > 2 else False
+        desc[b, 0] = off
+        if not valid:
+            desc[b, 3] = FLAG_INVALID
+            continue
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+            raise ValueError(f"collate_raw takes uint8 [T,H,W,3] frames, got {frames.dtype} {tuple(frames.shape)}")
+        if clip_len is None:
+            clip_len = frames.shape[0]
+        elif frames.shape[0] != clip_len:
+            raise ValueError(f"clips of one batch must have one length ({clip_len} and {frames.shape[0]} frames)")
+        desc[b, 1], desc[b, 2], desc[b, 3] = frames.shape[1], frames.shape[2], FLAG_FLIP if flip else 0
+        parts.append(frames.contiguous().view(-1))
+        off += parts[-1].numel()
+    packed = torch.cat(parts) if parts else torch.empty(0, dtype=torch.uint8)
+    return packed, desc
+
+
+class ClipResizer:
+    """Packed host frames -> resized, flipped, normalised fp32 clip [B,3,T,S,S] in HBM: one
+    H2D copy of the pixels, one of the descriptors, one launch (sm_frames_resize_normalize)."""
+
+    def __init__(self, image_size, mean=IMAGENET_MEAN, std=IMAGENET_STD, bgr_swap=True, device="cuda"):
+        hw = (image_size, image_size) if isinstance(image_size, int) else tuple(image_size)
+        self.out_hw = (int(hw[0]), int(hw[1]))
+        self.mean, self.std, self.bgr_swap, self.device = tuple(mean), tuple(std), bgr_swap, torch.device(device)
+
+    @staticmethod
+    def check(packed, desc, T):
+        """Host-side validation of the descriptors against the packed buffer (the kernel
+        bound-checks as well and writes zeros; a bad descriptor here is a loader bug)."""
+        from ._lib import KernelError
+        if packed.dtype != torch.uint8 or packed.dim() != 1:
+            raise KernelError("packed must be a 1-D uint8 tensor")
+        if desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != 4:
+            raise KernelError("desc must be an int64 [B,4] tensor")
+        if int(T) < 0:
+            raise KernelError("the clip length must not be negative")
+        n = packed.numel()
+        for b, (off, hs, ws, flags) in enumerate(desc.tolist()):
+            if flags & FLAG_INVALID:
+                continue
+            if not (1 <= hs <= MAX_SOURCE_SIDE and 1 <= ws <= MAX_SOURCE_SIDE):
+                raise KernelError(f"clip {b}: frame size {hs}x{ws} is outside [1, {MAX_SOURCE_SIDE}]")
+            if off < 0 or off + int(T) * hs * ws * 3 > n:
+                raise KernelError(f"clip {b}: bytes [{off}, {off + int(T) * hs * ws * 3}) leave the packed buffer "
+                                  f"of {n} bytes")
+
+    def __call__(self, packed, desc, T):
+        self.check(packed, desc, T)
+        p = packed.to(self.device, non_blocking=True)
+        d = desc.to(self.device, non_blocking=True)
+        return K.frames_resize_normalize(p.contiguous(), d.contiguous(), int(T), self.out_hw, self.mean, self.std,
+                                         self.bgr_swap)
 
 
 def resolve_cut_ties(noise, num_mask):

@@ -85,15 +85,16 @@ class SyntheticLoader:
 
 
 def split_loader(cfg, device):
-    """`dataset.split`: lines of `<frame directory> <label>`; frames decoded on the host and
-    normalised on the device (mae_loader.ClipNormalizer)."""
-    from .mae_loader import ClipNormalizer, LazyVideoMAEDataset
+    """`dataset.split`: lines of `<frame directory> <label>`; frames decoded on the host at
+    their own size, resized to `image_size` and normalised on the device
+    (mae_loader.ClipResizer)."""
+    from .mae_loader import ClipResizer, LazyVideoMAEDataset, collate_raw
     ds, rt = cfg["dataset"], cfg["runtime"]
     data = LazyVideoMAEDataset(ds["split"], clip_len=int(ds["clip_len"]), stride=int(ds["stride"]),
                                image_size=int(ds["image_size"]))
     with open(ds["split"]) as f:
         labels = [int(line.split()[1]) for line in f if line.strip()]
-    norm = ClipNormalizer(device=device)
+    norm = ClipResizer(int(ds["image_size"]), device=device)
 
     class Labelled(torch.utils.data.Dataset):
         def __len__(self):
@@ -104,8 +105,7 @@ def split_loader(cfg, device):
             return frames, valid, labels[i]
 
     def collate(batch):
-        return (torch.stack([b[0] for b in batch]), torch.tensor([bool(b[1]) for b in batch]),
-                torch.tensor([b[2] for b in batch]))
+        return collate_raw([b[:2] for b in batch]) + (torch.tensor([b[2] for b in batch]),)
 
     loader = torch.utils.data.DataLoader(Labelled(), batch_size=int(rt["batch_size"]), shuffle=False,
                                          num_workers=int(rt["num_workers"]), collate_fn=collate)
@@ -114,8 +114,8 @@ def split_loader(cfg, device):
         batch_size = loader.batch_size
 
         def __iter__(self):
-            for frames, valid, label in loader:
-                yield norm(frames, valid), label.to(device)
+            for packed, desc, label in loader:
+                yield norm(packed, desc, int(ds["clip_len"])), label.to(device)
 
     return Normalised()
 

@@ -482,24 +482,25 @@ class SyntheticClips:
 
 def split_loader(cfg, device):
     """Lines of `<frame directory> ...`: frames decoded on the host (LazyVideoMAEDataset with
-    transform=None) and normalised on the device, RGB order (ClipNormalizer(bgr_swap=False))."""
-    from .mae_loader import ClipNormalizer, LazyVideoMAEDataset, collate_frames
+    transform=None) at their own size, resized to `image_size` and normalised on the device,
+    RGB order (ClipResizer(bgr_swap=False))."""
+    from .mae_loader import ClipResizer, LazyVideoMAEDataset, collate_raw
     ds, tr = cfg["dataset"], cfg["training"]
     path = os.path.join(ds.get("split_root", ""), ds["train_split"])
     data = LazyVideoMAEDataset(path, clip_len=int(ds["clip_len"]), stride=int(ds["stride"]),
                                image_size=int(ds["image_size"]), transform=None)
     loader = torch.utils.data.DataLoader(data, batch_size=int(tr["batch_size"]), shuffle=True,
                                          num_workers=int(tr.get("num_workers", 4)), pin_memory=True, drop_last=True,
-                                         collate_fn=collate_frames)
-    norm = ClipNormalizer(bgr_swap=False, device=device)
+                                         collate_fn=collate_raw)
+    norm = ClipResizer(int(ds["image_size"]), bgr_swap=False, device=device)
 
     class Normalised:
         def __len__(self):
             return len(loader)
 
         def __iter__(self):
-            for frames, valid in loader:
-                yield norm(frames, valid)
+            for packed, desc in loader:
+                yield norm(packed, desc, int(ds["clip_len"]))
 
     return Normalised()
 

@@ -8,7 +8,8 @@ step, and every `log_interval` steps the masked-prediction std and throughput
 (log_interval * batch_size / elapsed).  `main()` honours `--config` (the
 reference hard-codes the path, :130) and runs the loop the reference's :168
 TypeError prevents.  The loader is the MI355X clip pipeline of mae_loader
-(uint8 frames, one H2D copy, sm_frames_normalize on the GPU); a loader that yields
+(uint8 frames at their own size, one H2D copy, sm_frames_resize_normalize on the GPU
+brings them to `dataset.image_size`); a loader that yields
 ready fp32 clips (the reference's transform path) is accepted as well.  Every 10
 epochs the reference's encoder-only file is written, plus a full training-state
 file (`checkpoint.py`) that `--resume` continues from.
@@ -36,7 +37,7 @@ from . import dist as smdist
 from . import ops as K    # every kernel launch through the torch.ops.ssl_mae dispatcher
 from .functions import mae_loss, masked_pred_std
 from .checkpoint import gather_rng_states, load_training_state, save_training_state
-from .mae_loader import ClipNormalizer, LazyVideoMAEDataset, collate_frames, tube_mask_with_index
+from .mae_loader import ClipNormalizer, ClipResizer, LazyVideoMAEDataset, collate_raw, tube_mask_with_index
 from .mae_vit_adapter import TinyVideoMAE
 from .optim import FusedAdamW, GradScaler
 from .tiny_vit import ENCODERS
@@ -85,14 +86,24 @@ def train_step(model, clip, optimizer, scaler, ssl_cfg, bf16=True):
     return loss, pred, idx
 
 
-def _to_clip(batch, device, normalizer):
-    """A loader batch -> fp32 clip [B,3,T,H,W] on the device: (uint8 frames, valid)
-    from the transform=None dataset goes through sm_frames_normalize; a tensor is a
-    ready clip (reference transform path)."""
+def _to_clip(batch, device, normalizer, clip_len=None):
+    """A loader batch -> fp32 clip [B,3,T,H,W] on the device: (packed uint8, desc) from
+    collate_raw goes through sm_frames_resize_normalize (`normalizer` a ClipResizer),
+    (uint8 frames [B,T,H,W,3], valid) from collate_frames through sm_frames_normalize (a
+    ClipNormalizer); a tensor is a ready clip (reference transform path)."""
     if isinstance(batch, (tuple, list)):
-        frames, valid = batch
-        return normalizer(frames, valid)
+        first, second = batch
+        if first.dim() == 1:
+            return normalizer(first, second, clip_len)
+        return normalizer(first, second)
     return batch.to(device, non_blocking=True)
+
+
+def _default_normalizer(batch, device, config):
+    """The input stage for a loader's batches when the caller passed none."""
+    if isinstance(batch, (tuple, list)) and batch[0].dim() == 1:
+        return ClipResizer(config["dataset"]["image_size"], device=device)
+    return ClipNormalizer(device=device)
 
 
 def _world():
@@ -111,8 +122,6 @@ def _mean_over_ranks(t):
 
 def train_one_epoch(model, loader, optimizer, scaler, epoch, device, config, writer, logger, normalizer=None):
     model.train()
-    if normalizer is None:
-        normalizer = ClipNormalizer(device=device)
     ssl_cfg = config["ssl"]
     train_cfg = config["training"]
     num_steps = len(loader)
@@ -121,7 +130,9 @@ def train_one_epoch(model, loader, optimizer, scaler, epoch, device, config, wri
     last_log = time.time()
     total_loss = 0.0
     for step, batch in enumerate(loader):
-        clip = _to_clip(batch, device, normalizer)
+        if normalizer is None:
+            normalizer = _default_normalizer(batch, device, config)
+        clip = _to_clip(batch, device, normalizer, config["dataset"]["clip_len"])
         loss, pred, idx = train_step(model, clip, optimizer, scaler, ssl_cfg)
         loss = _mean_over_ranks(loss)
         total_loss += loss.item()
@@ -149,12 +160,12 @@ def build_model(cfg, device="cuda"):
 
 def make_loader(ds, batch_size, num_workers=16, shuffle=True, sampler=None):
     """train_ssl_mae.py:154-161 (16 workers, pinned memory, prefetch 2) over the
-    uint8-frame dataset (collate_frames); `sampler` (data parallel: a
-    DistributedSampler) replaces the shuffle."""
+    uint8-frame dataset (collate_raw: clips packed at their own frame size);
+    `sampler` (data parallel: a DistributedSampler) replaces the shuffle."""
     kw = {"prefetch_factor": 2} if num_workers > 0 else {}
     return torch.utils.data.DataLoader(ds, batch_size=batch_size, shuffle=shuffle and sampler is None,
                                        sampler=sampler, num_workers=num_workers, pin_memory=True,
-                                       collate_fn=collate_frames, **kw)
+                                       collate_fn=collate_raw, **kw)
 
 
 class _RankZeroLogger:
@@ -215,7 +226,7 @@ def main(argv=None):
     # rank 0's weights and buffers everywhere; bucketed gradient all-reduce hooked into
     # the backward (side stream) and the optimizer (world > 1)
     smdist.setup_data_parallel(model, optimizer, world)
-    normalizer = ClipNormalizer(device=device)
+    normalizer = ClipResizer(cfg["dataset"]["image_size"], device=device)
     logger.info("=" * 50)
     logger.info(f"STARTING PRETRAINING | Total Epochs: {cfg['training']['epochs']}")
     logger.info(f"image size: {cfg['dataset']['image_size']} | Mask Ratio: {cfg['ssl']['mask_ratio']} | "
