@@ -586,6 +586,49 @@ int sm_fedavg_weighted_sum(int num_clients, const float* const* client_bufs, con
 int sm_fedavg_counters_max(int num_clients, const int64_t* const* client_counters, int64_t n, int64_t* out,
                            hipStream_t st);
 
+/* ---- FedAvg round exchange over a cohort's state entries where they live: one launch
+ * reads every source model's tensors and writes the result into every destination model's.
+ *
+ * FedAvg exchange table (DEVICE memory, 16-byte aligned, built once per cohort of P models,
+ * 1 <= P <= SM_FEDAVG_MAX_CLIENTS + 1; a segment is one state entry, laid out identically --
+ * same length, contiguous -- in every model):
+ *   SmFedTableHeader                       64 bytes
+ *   uint64_t addr[P][S]                    device address of segment s in model p
+ *   int64_t  seg_len[S]                    elements
+ *   int64_t  chunk_off[C]                  first element of the chunk within its segment,
+ *                                          a multiple of SM_FEDAVG_CHUNK_ELEMS
+ *   int32_t  chunk_seg[C]                  the chunk's segment; a chunk covers
+ *                                          min(SM_FEDAVG_CHUNK_ELEMS, seg_len - chunk_off) elements
+ *   zero padding to a multiple of 16 bytes
+ * total_bytes = 64 + 8 P S + 8 S + 12 C rounded up to 16.  The chunks together cover every
+ * element of every segment once.  elem_bytes is 4 (fp32 segments, sm_fedavg_exchange) or 8
+ * (int64 segments, sm_fedavg_exchange_counters); every address is a multiple of elem_bytes.
+ *
+ * sm_fedavg_exchange: for every element i of every segment, acc = +0, then in src order
+ * acc = fadd_rn(acc, fmul_rn(x_j[i], weights[j])) -- sm_fedavg_weighted_sum's operations in
+ * its order, so bit-identical to it -- stored to element i of the segment in every dst model.
+ * copy_only = 1 needs num_src == 1 and stores x_0[i] unchanged (a bit copy: -0 and NaN
+ * payloads survive; weights may be NULL).  src_models / dst_models (model indices into the
+ * table, 1 <= num_src <= SM_FEDAVG_MAX_CLIENTS, 1 <= num_dst <= SM_FEDAVG_MAX_CLIENTS + 1) and
+ * weights are HOST arrays.  A destination may also be a source: the lane that writes element i
+ * has loaded it from every source first.  A chunk moves as 16-byte vectors when its segment's
+ * base is 16-byte aligned in every model of the launch, else element by element; each segment's
+ * len % 4 tail is scalar.
+ * sm_fedavg_exchange_counters: the int64 max over the sources instead.
+ * Both read the table's header back (64 bytes, a stream synchronisation) and return -2 for bad
+ * counts, NULL arrays or table, a header that does not match table_bytes / the element size /
+ * the chunk size, or a model index outside [0, P). */
+#define SM_FEDAVG_CHUNK_ELEMS 2048
+#define SM_FEDAVG_TABLE_MAGIC 0x31424154444546LL /* "FEDTAB1" */
+typedef struct SmFedTableHeader {
+  int64_t magic, num_models, num_segments, num_chunks, elem_bytes, chunk_elems, total_bytes, reserved;
+} SmFedTableHeader;
+int sm_fedavg_exchange(int num_src, const int32_t* src_models, const float* weights, int num_dst,
+                       const int32_t* dst_models, const void* table, int64_t table_bytes, int copy_only,
+                       hipStream_t st);
+int sm_fedavg_exchange_counters(int num_src, const int32_t* src_models, int num_dst, const int32_t* dst_models,
+                                const void* table, int64_t table_bytes, hipStream_t st);
+
 /* ---- clip input pipeline (src/train_ssl_mae.py:137-141 PILToTensor + ConvertImageDtype +
  * Normalize; src/datasets/mae_loader.py:70-77 BGR swap img[[2,1,0]] and [C,T,H,W] stack).
  * frames uint8 [B][T][H][W][3] (decoded RGB) -> out fp32 [B][3][T][H][W],

@@ -11,6 +11,10 @@
   112^2, next to sm_frames_normalize at the same output size, eager torch ops, the host
   path on 16 threads and the 4.9 GB copy calibration (see `resize`).
 
+* `aux_bench.py fedround [--out profiles/fed_exchange.txt]`: one FedAvg round's exchange through
+  federated.FedCohort against run_fedavg's state_dict path, and the fused launches' bandwidth
+  against the copy calibration (see `fedround`).
+
 Prints one JSON line per kernel; run under rocprofv3 --kernel-trace --stats to
 cross-check the average launch durations."""
 import json
@@ -95,6 +99,18 @@ def _rounds(fn, reps, rounds):
 def _fmt(t):
     import statistics
     return f"{statistics.median(t):.3f} ms [{min(t):.3f} .. {max(t):.3f}]"
+
+
+def _copy_calibration(rounds):
+    """(report line, GB/s) of a 4.9 GB device-to-device copy, read + write."""
+    import statistics
+    n = int(4.9e9) // 4
+    a, b = torch.empty(n, device="cuda"), torch.empty(n, device="cuda")
+    b.copy_(a)
+    torch.cuda.synchronize()
+    tc = _rounds(lambda: b.copy_(a), 5, rounds)
+    gbs = 2 * n * 4 / statistics.median(tc) / 1e6
+    return f"copy calibration (4.9 GB device-to-device, read + write): {_fmt(tc)}  {gbs:.0f} GB/s", gbs
 
 
 def resize(out_path=None, B=256, T=8, reps=20, rounds=5, host_threads=16):
@@ -184,13 +200,90 @@ def resize(out_path=None, B=256, T=8, reps=20, rounds=5, host_threads=16):
                      f"{_fmt(th)}  {statistics.median(th) / mr:.0f}x the kernel")
         del src, same, out, out2, packed
         torch.cuda.empty_cache()
-    n = int(4.9e9) // 4
-    a, b = torch.empty(n, device=dev), torch.empty(n, device=dev)
-    b.copy_(a)
-    torch.cuda.synchronize()
-    tc = _rounds(lambda: b.copy_(a), 5, rounds)
-    lines.append(f"copy calibration (4.9 GB device-to-device, read + write): {_fmt(tc)}  "
-                 f"{2 * n * 4 / statistics.median(tc) / 1e6:.0f} GB/s")
+    lines.append(_copy_calibration(rounds)[0])
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+
+
+def fedround(out_path=None, reps=5, rounds=5, num_classes=101):
+    """One FedAvg round's exchange (broadcast + aggregate) over VideoClassifier models at 112^2
+    that have each run one forward (parameters in their flat buffers), K = 4 and K = 8 selected
+    clients: (a) federated.FedCohort, one launch each way, against (b) run_fedavg's path in the
+    same process -- K strict load_state_dict broadcasts, then fedavg_aggregate (torch.cat
+    gathers, one launch, un-flatten, load_state_dict).  The fused launches alone are timed
+    through kernels.fedavg_exchange (each call includes its 64-byte header read-back); bytes
+    moved = (sources + destinations) x fp32 state bytes.  Ends with the 4.9 GB copy calibration."""
+    import statistics
+    from ssl_mae_amd.finetune import VideoClassifier
+    lines = [f"device: {torch.cuda.get_device_name(0)}; VideoClassifier({num_classes}) at 112^2; {rounds} rounds of "
+             f"{reps} exchanges, median [min .. max]"]
+    clip = torch.randn(1, 3, 1, 112, 112, device="cuda")
+    models = []
+    for s in range(9):
+        torch.manual_seed(s)
+        m = VideoClassifier(num_classes, img_size=112).cuda().eval()
+        with torch.no_grad():
+            m(clip)
+        models.append(m)
+    glob = models[0]
+    results = []
+    for k in (4, 8):
+        clients = models[1:k + 1]
+        sel = list(range(k))
+        sizes = [100.0 + 10 * i for i in sel]
+        cohort = F.FedCohort(glob, clients)
+        fbytes = sum(v.numel() * 4 for v in glob.state_dict().values() if v.is_floating_point())
+        entries = len(glob.state_dict())
+
+        def fused():
+            cohort.broadcast(sel)
+            cohort.aggregate(sel, sizes)
+
+        def parent():
+            g = {n: v.detach().clone() for n, v in glob.state_dict().items()}
+            for c in clients:
+                c.load_state_dict(g, strict=True)
+            states = [{n: v.detach() for n, v in c.state_dict().items()} for c in clients]
+            F.fedavg_aggregate(glob, states, sizes)
+
+        norm = F._norm_weights(sizes, float(sum(sizes)))
+        src = [c + 1 for c in sel]
+
+        def k_aggregate():
+            K.fedavg_exchange(src, norm, [0], cohort._float_table)
+
+        def k_broadcast():
+            K.fedavg_exchange([0], [1.0], src, cohort._float_table, copy_only=True)
+
+        for fn in (fused, parent, k_aggregate, k_broadcast):
+            fn()
+        torch.cuda.synchronize()
+        tf, tp = [], []
+        for _ in range(rounds):                         # alternate the two paths
+            tf += _rounds(fused, reps, 1)
+            tp += _rounds(parent, reps, 1)
+        ta, tb = _rounds(k_aggregate, reps, rounds), _rounds(k_broadcast, reps, rounds)
+        gb = (k + 1) * fbytes / 1e9
+        ga, gbb = gb / statistics.median(ta) * 1e3, gb / statistics.median(tb) * 1e3
+        assert cohort.rebuilds == 1
+        lines.append(f"K={k} selected clients, {entries} state entries, {fbytes / 2 ** 20:.1f} MiB fp32 state per model:")
+        lines.append(f"  (a) FedCohort broadcast + aggregate: {_fmt(tf)}")
+        lines.append(f"  (b) load_state_dict broadcast + fedavg_aggregate: {_fmt(tp)}  "
+                     f"{statistics.median(tp) / statistics.median(tf):.1f}x (a)")
+        lines.append(f"  fused aggregate launch ({k} sources -> 1 destination): {_fmt(ta)}  {gb:.3f} GB moved  {ga:.0f} GB/s")
+        lines.append(f"  fused broadcast launch (1 source -> {k} destinations): {_fmt(tb)}  {gb:.3f} GB moved  {gbb:.0f} GB/s")
+        results.append((k, ga, gbb))
+    del models, clients, cohort
+    torch.cuda.empty_cache()
+    line, copy_gbs = _copy_calibration(rounds)
+    lines.append(line)
+    for k, ga, gbb in results:
+        lines.append(f"K={k}: fused aggregate at {ga / copy_gbs:.2f}, fused broadcast at {gbb / copy_gbs:.2f} of the copy "
+                     "calibration's bandwidth")
     text = "\n".join(lines) + "\n"
     print(text, end="")
     if out_path:
@@ -200,8 +293,9 @@ def resize(out_path=None, B=256, T=8, reps=20, rounds=5, host_threads=16):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "resize":
-        resize(sys.argv[3] if len(sys.argv) > 3 and sys.argv[2] == "--out" else None)
+    if len(sys.argv) > 1 and sys.argv[1] in ("resize", "fedround"):
+        out = sys.argv[3] if len(sys.argv) > 3 and sys.argv[2] == "--out" else None
+        {"resize": resize, "fedround": fedround}[sys.argv[1]](out)
     else:
         main()
         frames()

@@ -75,7 +75,239 @@ __global__ void counters_max_kernel(ClientCounters c, int k, int64_t n, int64_t*
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
+// ---- multi-tensor exchange: one launch over a cohort's state entries where they live.
+// The table (sm_api.h "FedAvg exchange table") maps every chunk of kChunk elements to a
+// segment (one state entry) and an offset in it; a block takes whole chunks, grid-stride.
+// Sources and destinations may alias (in-place aggregation): a lane loads its elements
+// from every source before its first store, lanes own disjoint elements, and no pointer
+// here is __restrict__.
+constexpr int kChunk = SM_FEDAVG_CHUNK_ELEMS;
+constexpr int kVecPerLane = kChunk / (256 * 4);   // float4 groups per lane per source
+static_assert(kChunk % 1024 == 0, "a chunk is a whole number of 256-lane float4 rows");
+
+struct ExchangeArgs {
+  int32_t src[kMaxClients];
+  float w[kMaxClients];
+  int32_t dst[kMaxClients + 1];
+  int num_src, num_dst;
+};
+
+struct TableView {
+  int64_t S, C;
+  const uint64_t* addr;      // [P][S]
+  const int64_t* seg_len;    // [S]
+  const int64_t* chunk_off;  // [C]
+  const int32_t* chunk_seg;  // [C]
+};
+
+SM_DEV TableView table_view(const unsigned char* tab) {
+  const SmFedTableHeader* h = (const SmFedTableHeader*)tab;
+  TableView t;
+  t.S = h->num_segments;
+  t.C = h->num_chunks;
+  t.addr = (const uint64_t*)(tab + sizeof(SmFedTableHeader));
+  t.seg_len = (const int64_t*)(t.addr + h->num_models * t.S);
+  t.chunk_off = t.seg_len + t.S;
+  t.chunk_seg = (const int32_t*)(t.chunk_off + t.C);
+  return t;
+}
+
+// Elements [off, off + n) of segment `seg`: false when the chunk entry points outside it.
+SM_DEV bool chunk_range(const TableView& t, int64_t c, int64_t& seg, int64_t& off, int64_t& n) {
+  seg = t.chunk_seg[c];
+  off = t.chunk_off[c];
+  if (seg < 0 || seg >= t.S || off < 0) return false;
+  const int64_t len = t.seg_len[seg];
+  if (off >= len) return false;
+  n = len - off < kChunk ? len - off : kChunk;
+  return true;
+}
+
+// KC > 0: source count known at compile time (all KC * kVecPerLane loads of a lane are issued
+// before the first multiply-add); KC == 0: runtime count.  COPY: one source, stored as loaded.
+template <int KC, bool COPY>
+SM_DEV float exchange_one(const ExchangeArgs& a, const TableView& t, int64_t seg, int k, int64_t i) {
+  if constexpr (COPY) {
+    return ((const float*)t.addr[a.src[0] * t.S + seg])[i];
+  } else {
+    float acc = 0.f;
+    if constexpr (KC > 0) {
+      float x[KC];
+#pragma unroll
+      for (int j = 0; j < KC; ++j) x[j] = ((const float*)t.addr[a.src[j] * t.S + seg])[i];
+#pragma unroll
+      for (int j = 0; j < KC; ++j) acc = __fadd_rn(acc, __fmul_rn(x[j], a.w[j]));
+    } else {
+      for (int j = 0; j < k; ++j)
+        acc = __fadd_rn(acc, __fmul_rn(((const float*)t.addr[a.src[j] * t.S + seg])[i], a.w[j]));
+    }
+    return acc;
+  }
+}
+
+template <int KC, bool COPY>
+__global__ void __launch_bounds__(256) fedavg_exchange_kernel(ExchangeArgs a, const unsigned char* tab) {
+  const TableView t = table_view(tab);
+  const int k = KC > 0 ? KC : a.num_src;
+  const int tid = threadIdx.x;
+  for (int64_t c = blockIdx.x; c < t.C; c += gridDim.x) {
+    int64_t seg, off, n;
+    if (!chunk_range(t, c, seg, off, n)) continue;
+    uint64_t bits = (uint64_t)off * 4;   // vector path: this chunk 16-byte aligned in every model of the launch
+    for (int j = 0; j < k; ++j) bits |= t.addr[a.src[j] * t.S + seg];
+    for (int d = 0; d < a.num_dst; ++d) bits |= t.addr[a.dst[d] * t.S + seg];
+    if ((bits & 15u) != 0) {
+      for (int64_t i = off + tid; i < off + n; i += 256) {
+        const float v = exchange_one<KC, COPY>(a, t, seg, k, i);
+        for (int d = 0; d < a.num_dst; ++d) ((float*)t.addr[a.dst[d] * t.S + seg])[i] = v;
+      }
+      continue;
+    }
+    const int64_t n4 = n / 4;
+    f32x4 acc[kVecPerLane] = {};
+    if constexpr (COPY) {
+      const f32x4* p = (const f32x4*)((const float*)t.addr[a.src[0] * t.S + seg] + off);
+#pragma unroll
+      for (int u = 0; u < kVecPerLane; ++u)
+        if (tid + 256 * u < n4) acc[u] = __builtin_nontemporal_load(p + tid + 256 * u);
+    } else if constexpr (KC > 0) {
+      f32x4 x[KC][kVecPerLane];
+#pragma unroll
+      for (int j = 0; j < KC; ++j) {
+        const f32x4* p = (const f32x4*)((const float*)t.addr[a.src[j] * t.S + seg] + off);
+#pragma unroll
+        for (int u = 0; u < kVecPerLane; ++u)
+          x[j][u] = tid + 256 * u < n4 ? __builtin_nontemporal_load(p + tid + 256 * u) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+#pragma unroll
+      for (int u = 0; u < kVecPerLane; ++u) {
+        acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < KC; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[u][e] = __fadd_rn(acc[u][e], __fmul_rn(x[j][u][e], a.w[j]));
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < kVecPerLane; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < k; ++j) {
+        const f32x4* p = (const f32x4*)((const float*)t.addr[a.src[j] * t.S + seg] + off);
+        f32x4 x[kVecPerLane];
+#pragma unroll
+        for (int u = 0; u < kVecPerLane; ++u)
+          x[u] = tid + 256 * u < n4 ? __builtin_nontemporal_load(p + tid + 256 * u) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < kVecPerLane; ++u)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[u][e] = __fadd_rn(acc[u][e], __fmul_rn(x[u][e], a.w[j]));
+      }
+    }
+    // the segment's scalar tail (n % 4 elements, last chunk only): loaded before any store too
+    const int64_t ti = off + n4 * 4 + tid;
+    const bool has_tail = ti < off + n;
+    float tail = 0.f;
+    if (has_tail) tail = exchange_one<KC, COPY>(a, t, seg, k, ti);
+    for (int d = 0; d < a.num_dst; ++d) {
+      float* q = (float*)t.addr[a.dst[d] * t.S + seg];
+#pragma unroll
+      for (int u = 0; u < kVecPerLane; ++u)
+        if (tid + 256 * u < n4) __builtin_nontemporal_store(acc[u], (f32x4*)(q + off) + tid + 256 * u);
+      if (has_tail) q[ti] = tail;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) fedavg_exchange_counters_kernel(ExchangeArgs a, const unsigned char* tab) {
+  const TableView t = table_view(tab);
+  for (int64_t c = blockIdx.x; c < t.C; c += gridDim.x) {
+    int64_t seg, off, n;
+    if (!chunk_range(t, c, seg, off, n)) continue;
+    for (int64_t i = off + threadIdx.x; i < off + n; i += 256) {
+      int64_t m = ((const int64_t*)t.addr[a.src[0] * t.S + seg])[i];
+      for (int j = 1; j < a.num_src; ++j) {
+        const int64_t v = ((const int64_t*)t.addr[a.src[j] * t.S + seg])[i];
+        m = v > m ? v : m;
+      }
+      for (int d = 0; d < a.num_dst; ++d) ((int64_t*)t.addr[a.dst[d] * t.S + seg])[i] = m;
+    }
+  }
+}
+
+// Counts, model indices and the table's header (read back from the device: 64 bytes, once
+// per launch) against table_bytes and the entry point's element size.  0, or -2.
+int exchange_args(int num_src, const int32_t* src_models, const float* weights, int num_dst,
+                  const int32_t* dst_models, const void* table, int64_t table_bytes, int elem_bytes,
+                  hipStream_t st, ExchangeArgs& a, int64_t& chunks) {
+  if (num_src < 1 || num_src > kMaxClients || num_dst < 1 || num_dst > kMaxClients + 1) return -2;
+  if (!src_models || !dst_models || !table || table_bytes < (int64_t)sizeof(SmFedTableHeader)) return -2;
+  SmFedTableHeader h;
+  hipError_t e = hipMemcpyAsync(&h, table, sizeof(h), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return (int)e;
+  if (h.magic != SM_FEDAVG_TABLE_MAGIC || h.elem_bytes != elem_bytes || h.chunk_elems != kChunk) return -2;
+  if (h.num_models < 1 || h.num_models > kMaxClients + 1 || h.num_segments < 0 || h.num_chunks < 0) return -2;
+  if (h.num_segments > (int64_t)1 << 31 || h.num_chunks > (int64_t)1 << 40) return -2;
+  int64_t bytes = (int64_t)sizeof(SmFedTableHeader) + 8 * h.num_models * h.num_segments + 8 * h.num_segments +
+                  12 * h.num_chunks;
+  bytes = (bytes + 15) / 16 * 16;
+  if (h.total_bytes != bytes || table_bytes != bytes) return -2;
+  a = ExchangeArgs{};
+  for (int j = 0; j < num_src; ++j) {
+    if (src_models[j] < 0 || src_models[j] >= h.num_models) return -2;
+    a.src[j] = src_models[j];
+    a.w[j] = weights ? weights[j] : 0.f;
+  }
+  for (int d = 0; d < num_dst; ++d) {
+    if (dst_models[d] < 0 || dst_models[d] >= h.num_models) return -2;
+    a.dst[d] = dst_models[d];
+  }
+  a.num_src = num_src;
+  a.num_dst = num_dst;
+  chunks = h.num_chunks;
+  return 0;
+}
+
 }  // namespace
+
+extern "C" int sm_fedavg_exchange(int num_src, const int32_t* src_models, const float* weights, int num_dst,
+                                  const int32_t* dst_models, const void* table, int64_t table_bytes, int copy_only,
+                                  hipStream_t st) {
+  if (copy_only ? num_src != 1 : !weights) return -2;
+  ExchangeArgs a;
+  int64_t chunks = 0;
+  const int rc = exchange_args(num_src, src_models, weights, num_dst, dst_models, table, table_bytes, 4, st, a, chunks);
+  if (rc != 0 || chunks == 0) return rc;
+  // 8 resident 256-lane blocks per CU on 256 CUs, grid-stride over chunks beyond that.
+  const dim3 g((unsigned)(chunks < 2048 ? chunks : 2048)), b(256);
+  const unsigned char* tab = (const unsigned char*)table;
+  if (copy_only) {
+    hipLaunchKernelGGL((fedavg_exchange_kernel<1, true>), g, b, 0, st, a, tab);
+  } else {
+    switch (num_src) {
+      case 1: hipLaunchKernelGGL((fedavg_exchange_kernel<1, false>), g, b, 0, st, a, tab); break;
+      case 2: hipLaunchKernelGGL((fedavg_exchange_kernel<2, false>), g, b, 0, st, a, tab); break;
+      case 3: hipLaunchKernelGGL((fedavg_exchange_kernel<3, false>), g, b, 0, st, a, tab); break;
+      case 4: hipLaunchKernelGGL((fedavg_exchange_kernel<4, false>), g, b, 0, st, a, tab); break;
+      case 8: hipLaunchKernelGGL((fedavg_exchange_kernel<8, false>), g, b, 0, st, a, tab); break;
+      default: hipLaunchKernelGGL((fedavg_exchange_kernel<0, false>), g, b, 0, st, a, tab); break;
+    }
+  }
+  SM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sm_fedavg_exchange_counters(int num_src, const int32_t* src_models, int num_dst,
+                                           const int32_t* dst_models, const void* table, int64_t table_bytes,
+                                           hipStream_t st) {
+  ExchangeArgs a;
+  int64_t chunks = 0;
+  const int rc = exchange_args(num_src, src_models, nullptr, num_dst, dst_models, table, table_bytes, 8, st, a, chunks);
+  if (rc != 0 || chunks == 0) return rc;
+  hipLaunchKernelGGL(fedavg_exchange_counters_kernel, dim3((unsigned)(chunks < 2048 ? chunks : 2048)), dim3(256), 0,
+                     st, a, (const unsigned char*)table);
+  SM_CHECK_LAUNCH();
+  return 0;
+}
 
 extern "C" int sm_fedavg_weighted_sum(int num_clients, const float* const* client_bufs, const float* weights,
                                       int64_t n, float* out, hipStream_t st) {

@@ -145,6 +145,8 @@ _SIGS = {
                           _c_i32, _c_p]),
     "sm_fedavg_weighted_sum": (_c_i32, [_c_i32, _c_p, _c_p, _c_i64, _c_p, _c_p]),
     "sm_fedavg_counters_max": (_c_i32, [_c_i32, _c_p, _c_i64, _c_p, _c_p]),
+    "sm_fedavg_exchange": (_c_i32, [_c_i32, _c_p, _c_p, _c_i32, _c_p, _c_p, _c_i64, _c_i32, _c_p]),
+    "sm_fedavg_exchange_counters": (_c_i32, [_c_i32, _c_p, _c_i32, _c_p, _c_p, _c_i64, _c_p]),
     "sm_frames_normalize": (_c_i32, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_i32, _c_p, _c_p]),
     "sm_frames_resize_normalize": (_c_i32, [_c_p, _c_p, _c_i64, _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_i32,
                                             _c_p, _c_p]),

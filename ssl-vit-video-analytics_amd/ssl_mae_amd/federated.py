@@ -121,6 +121,128 @@ def _unflat(flat, keys, like, dst):
         off += n
 
 
+# ------------------------------------------------------------------ one-launch round exchange
+def _state_slots(model):
+    """[(state_dict key, the owning module's parameter or buffer dict, name)]: where the tensors
+    state_dict() returns live.  Reading them from there skips building the OrderedDict and its
+    detached aliases, and the module walk, on every exchange (a few hundred entries per
+    VideoClassifier, looked up twice per round per model)."""
+    out = []
+    for prefix, mod in model.named_modules():
+        pre = prefix + "." if prefix else ""
+        out += [(pre + name, mod._parameters, name) for name, p in mod._parameters.items() if p is not None]
+        out += [(pre + name, mod._buffers, name) for name, b in mod._buffers.items()
+                if b is not None and name not in mod._non_persistent_buffers_set]
+    return out
+
+
+class FedCohort:
+    """A global model and its client models on one GPU, exchanged in place: `broadcast` and
+    `aggregate` each take one sm_fedavg_exchange launch over the fp32 entries (plus one
+    sm_fedavg_exchange_counters launch over the num_batches_tracked entries) that reads the
+    source models' tensors where they live and writes into the destination models' tensors,
+    instead of run_fedavg's load_state_dict copies, torch.cat gathers and un-flatten.  The
+    arithmetic and its order are fedavg_aggregate's, so the states agree bit for bit.
+
+    Table model 0 is the global model, model c + 1 is client c.  The tables hold device
+    addresses; parameter storage moves (the first forward re-homes the backbone's parameters
+    into its flat buffer, `.to()` moves everything), so every exchange compares the
+    participating tensors' addresses against the tables' host copy and rebuilds on a mismatch.
+    It follows tensors that move, not sub-modules that are replaced: build a new cohort then."""
+
+    def __init__(self, global_model, client_models):
+        self.global_model = global_model
+        self.client_models = list(client_models)
+        self.models = [global_model] + self.client_models
+        if not 1 <= len(self.client_models) <= K.FEDAVG_MAX_CLIENTS:
+            raise RuntimeError(f"[ERROR] FedCohort takes 1..{K.FEDAVG_MAX_CLIENTS} client models, "
+                               f"got {len(self.client_models)}")
+        states = [m.state_dict() for m in self.models]
+        ref = states[0]
+        for i, st in enumerate(states):
+            if list(st) != list(ref):
+                raise RuntimeError(f"[ERROR] FedCohort: client {i - 1} state_dict keys differ from the global model's")
+            for k, v in st.items():
+                if v.device.type != "cuda" or v.device != next(iter(ref.values())).device:
+                    raise RuntimeError("[ERROR] FedCohort needs every model on one cuda device "
+                                       f"({k} of model {i} is on {v.device})")
+                if v.shape != ref[k].shape or v.dtype != ref[k].dtype:
+                    raise RuntimeError(f"[ERROR] FedCohort: {k} of client {i - 1} is {tuple(v.shape)} {v.dtype}, "
+                                       f"the global model's is {tuple(ref[k].shape)} {ref[k].dtype}")
+        self.float_keys, self.count_keys, self.other_keys = [], [], []
+        for k, v in ref.items():
+            if _is_float_tensor(v):
+                if v.dtype != torch.float32:
+                    raise RuntimeError(f"FedCohort exchanges fp32 state only; {k} is {v.dtype} "
+                                       "(use fedavg_aggregate, which follows the reference for any float dtype)")
+                self.float_keys.append(k)
+            elif "num_batches_tracked" in k:
+                if v.dtype != torch.int64:
+                    raise RuntimeError(f"FedCohort: counter {k} is {v.dtype}, expected int64")
+                self.count_keys.append(k)
+            else:
+                self.other_keys.append(k)
+        self._slots = [_state_slots(m) for m in self.models]
+        if any([k for k, _, _ in sl] != list(ref) for sl in self._slots):
+            raise RuntimeError("[ERROR] FedCohort: a model's state_dict() is not its modules' parameters and "
+                               "persistent buffers (state_dict hooks are not supported)")
+        self.rebuilds = 0
+        self._build()
+
+    def _entries(self, p):
+        return {k: d[name] for k, d, name in self._slots[p]}
+
+    def _build(self):
+        ents = [self._entries(p) for p in range(len(self.models))]
+        self._float_table, self._float_addr = K.fedavg_exchange_table(
+            [[e[k].detach() for k in self.float_keys] for e in ents], torch.float32)
+        self._count_table, self._count_addr = K.fedavg_exchange_table(
+            [[e[k].detach() for k in self.count_keys] for e in ents], torch.int64)
+        self.rebuilds += 1
+
+    def _fresh(self, p, ents):
+        nf, nc = len(self.float_keys), len(self.count_keys)
+        return (all(ents[k].data_ptr() == a for k, a in zip(self.float_keys, self._float_addr[p * nf:(p + 1) * nf]))
+                and all(ents[k].data_ptr() == a
+                        for k, a in zip(self.count_keys, self._count_addr[p * nc:(p + 1) * nc])))
+
+    @torch.no_grad()
+    def exchange(self, src, weights, dst, copy_only=False):
+        """Table-model indices: sources (in accumulation order), their normalised fp32 weights,
+        destinations."""
+        ents = {p: self._entries(p) for p in dict.fromkeys(list(src) + list(dst))}
+        if not all(self._fresh(p, e) for p, e in ents.items()):
+            self._build()
+        if self.float_keys:
+            K.fedavg_exchange([ents[p][k].detach() for p in dst for k in self.float_keys], src, weights, dst,
+                              self._float_table, copy_only)
+        if self.count_keys:
+            K.fedavg_exchange_counters([ents[p][k].detach() for p in dst for k in self.count_keys], src, dst,
+                                       self._count_table)
+        for k in self.other_keys:        # the reference's "first client" rule (fed_loop.py:56-58)
+            for p in dst:
+                if p != src[0]:
+                    ents[p][k].copy_(ents[src[0]][k])
+
+    def aggregate(self, selected, client_weights, also=()):
+        """FedAvg of the clients `selected` (in that order) into the global model and into the
+        clients `also`, which may be among `selected`."""
+        total_w = _check(selected, client_weights)
+        norm = _norm_weights(client_weights, total_w)
+        self.exchange(self._clients(selected), norm, [0] + self._clients(also))
+
+    def broadcast(self, selected):
+        """The global model's state, bit for bit, into the clients `selected`."""
+        if len(selected):
+            self.exchange([0], [1.0], self._clients(selected), copy_only=True)
+
+    def _clients(self, ids):
+        for c in ids:
+            if not 0 <= int(c) < len(self.client_models):
+                raise RuntimeError(f"[ERROR] FedCohort: no client {c} (clients 0..{len(self.client_models) - 1})")
+        return [int(c) + 1 for c in ids]
+
+
 # ------------------------------------------------------------------ multi-GPU (C5)
 def fedavg_allgather(model, weight, group=None, combine=None):
     """Every rank is one client: replace `model`'s state on every rank with the
@@ -194,6 +316,26 @@ def estimate_comm_mb_per_round(global_state, num_clients_participating):
 
 
 # ------------------------------------------------------------------ host loop (fed_loop.py:65-150)
+def _logger(log_f):
+    def log(msg):
+        print(msg)
+        if log_f:
+            log_f.write(msg + "\n")
+            log_f.flush()
+    return log
+
+
+def _round_record(log, r, selected, losses, global_state, top1, top5):
+    """fed_loop.py:125-147: the round's record and its log line."""
+    comm_total_mb, model_mb = estimate_comm_mb_per_round(global_state, num_clients_participating=len(selected))
+    rec = {"round": r, "val_top1": float(top1), "val_top5": float(top5),
+           "avg_local_loss": float(sum(losses) / max(1, len(losses))), "clients": int(len(selected)),
+           "model_mb": float(model_mb), "comm_mb_round": float(comm_total_mb)}
+    log(f"[INFO] Round {r} val_top1={top1:.4f} val_top5={top5:.4f} "
+        f"avg_local_loss={rec['avg_local_loss']:.4f} comm_mb={comm_total_mb:.2f}")
+    return rec
+
+
 def run_fedavg(global_model, client_models, client_loaders, client_sizes, evaluate_fn, device, rounds=10,
                client_fraction=1.0, amp=True, log_f=None):
     """fed_loop.py:65-150: each round samples clients with random.Random(42),
@@ -202,12 +344,7 @@ def run_fedavg(global_model, client_models, client_loaders, client_sizes, evalua
     num_clients = len(client_models)
     rng = random.Random(42)
     records = []
-
-    def log(msg):
-        print(msg)
-        if log_f:
-            log_f.write(msg + "\n")
-            log_f.flush()
+    log = _logger(log_f)
 
     for r in range(1, int(rounds) + 1):
         m = max(1, int(num_clients * float(client_fraction)))
@@ -222,12 +359,29 @@ def run_fedavg(global_model, client_models, client_loaders, client_sizes, evalua
             states.append({k: v.detach() for k, v in client_models[cid].state_dict().items()})
             weights.append(float(client_sizes[cid]))
         new_state = fedavg_aggregate(global_model, states, weights)
-        comm_total_mb, model_mb = estimate_comm_mb_per_round(new_state, num_clients_participating=len(selected))
         top1, top5 = evaluate_fn(global_model)
-        rec = {"round": r, "val_top1": float(top1), "val_top5": float(top5),
-               "avg_local_loss": float(sum(losses) / max(1, len(losses))), "clients": int(len(selected)),
-               "model_mb": float(model_mb), "comm_mb_round": float(comm_total_mb)}
-        records.append(rec)
-        log(f"[INFO] Round {r} val_top1={top1:.4f} val_top5={top5:.4f} "
-            f"avg_local_loss={rec['avg_local_loss']:.4f} comm_mb={comm_total_mb:.2f}")
+        records.append(_round_record(log, r, selected, losses, new_state, top1, top5))
+    return records
+
+
+def run_fedavg_fused(global_model, client_models, client_loaders, client_sizes, evaluate_fn, device, rounds=10,
+                     client_fraction=1.0, amp=True, log_f=None):
+    """run_fedavg with the round's exchange through a FedCohort: the same sampled clients, log
+    lines and records, and bit-identical model states, with one broadcast launch and one
+    aggregation launch per round in place of the state_dict copies."""
+    num_clients = len(client_models)
+    rng = random.Random(42)
+    records = []
+    cohort = FedCohort(global_model, client_models)
+    log = _logger(log_f)
+
+    for r in range(1, int(rounds) + 1):
+        m = max(1, int(num_clients * float(client_fraction)))
+        selected = rng.sample(list(range(num_clients)), m)
+        log(f"[INFO] Round {r}/{rounds} selected_clients={selected}")
+        cohort.broadcast(selected)
+        losses = [float(client_loaders[cid]["update_fn"](client_models[cid])) for cid in selected]
+        cohort.aggregate(selected, [float(client_sizes[cid]) for cid in selected])
+        top1, top5 = evaluate_fn(global_model)
+        records.append(_round_record(log, r, selected, losses, global_model.state_dict(), top1, top5))
     return records

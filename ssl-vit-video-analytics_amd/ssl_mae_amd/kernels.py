@@ -977,6 +977,80 @@ def fedavg_counters_max(bufs, out=None):
     return out
 
 
+FEDAVG_MAX_CLIENTS = 32
+FEDAVG_CHUNK_ELEMS = 2048                    # SM_FEDAVG_CHUNK_ELEMS
+_FEDAVG_TABLE_MAGIC = 0x31424154444546      # SM_FEDAVG_TABLE_MAGIC
+
+
+def fedavg_exchange_table(models, dtype):
+    """The device table of sm_fedavg_exchange (dtype fp32) / sm_fedavg_exchange_counters (int64)
+    for a cohort: `models` is P lists of S tensors, segment s laid out identically in every
+    model.  Returns (uint8 device tensor, host list of the P*S addresses); the layout is
+    documented in include/sm_api.h."""
+    import numpy as np
+    P = len(models)
+    if P < 1 or P > FEDAVG_MAX_CLIENTS + 1:
+        raise _lib.KernelError(f"fedavg_exchange_table: {P} models, 1..{FEDAVG_MAX_CLIENTS + 1} supported")
+    S = len(models[0])
+    if dtype not in (torch.float32, torch.int64):
+        raise _lib.KernelError("fedavg_exchange_table: fp32 or int64 segments")
+    first = next((t for m in models for t in m), None)
+    device = first.device if first is not None else torch.device("cuda", torch.cuda.current_device())
+    for m in models:
+        if len(m) != S:
+            raise _lib.KernelError("fedavg_exchange_table: every model needs the same segments")
+        _chk(*m)
+        for t, t0 in zip(m, models[0]):
+            if t.dtype != dtype or t.shape != t0.shape or not t.is_contiguous() or t.device != device:
+                raise _lib.KernelError("fedavg_exchange_table: a segment must be contiguous, of the table's dtype "
+                                       "and of one shape on one device in every model")
+    seg_len = np.array([t.numel() for t in models[0]], dtype=np.int64)
+    n_chunks = (seg_len + FEDAVG_CHUNK_ELEMS - 1) // FEDAVG_CHUNK_ELEMS
+    chunk_seg = np.repeat(np.arange(S, dtype=np.int32), n_chunks)
+    first_chunk = np.cumsum(n_chunks) - n_chunks
+    chunk_off = (np.arange(len(chunk_seg), dtype=np.int64) - np.repeat(first_chunk, n_chunks)) * FEDAVG_CHUNK_ELEMS
+    addr = np.array([t.data_ptr() for m in models for t in m], dtype=np.uint64)
+    C = len(chunk_seg)
+    total = (64 + 8 * P * S + 8 * S + 12 * C + 15) // 16 * 16
+    elem = 4 if dtype == torch.float32 else 8
+    header = np.array([_FEDAVG_TABLE_MAGIC, P, S, C, elem, FEDAVG_CHUNK_ELEMS, total, 0], dtype=np.int64)
+    raw = b"".join(a.tobytes() for a in (header, addr, seg_len, chunk_off.astype(np.int64), chunk_seg))
+    raw += b"\0" * (total - len(raw))
+    table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
+    return table, addr.tolist()
+
+
+def _fedavg_exchange_call(name, src_models, weights, dst_models, table, extra):
+    import ctypes
+    _chk(table)
+    if table.dtype != torch.uint8 or not table.is_contiguous():
+        raise _lib.KernelError(f"{name}: the table is a contiguous uint8 device tensor (fedavg_exchange_table)")
+    src = (ctypes.c_int32 * max(1, len(src_models)))(*[int(i) for i in src_models])
+    dst = (ctypes.c_int32 * max(1, len(dst_models)))(*[int(i) for i in dst_models])
+    args = [len(src_models), ctypes.cast(src, ctypes.c_void_p)]
+    if weights is not None:
+        ws = (ctypes.c_float * max(1, len(weights)))(*[float(w) for w in weights])
+        args.append(ctypes.cast(ws, ctypes.c_void_p))
+    args += [len(dst_models), ctypes.cast(dst, ctypes.c_void_p), ptr(table), table.numel()] + extra + [stream()]
+    call("sm_" + name, *args)
+
+
+def fedavg_exchange(src_models, weights, dst_models, table, copy_only=False):
+    """One launch over an fp32 cohort table: the weighted sum of the source models' segments in
+    source order (fedavg_weighted_sum's arithmetic, bit for bit) -- or, with copy_only, the one
+    source's bits -- written into every destination model's segments, which may be sources too."""
+    if not copy_only and len(weights) != len(src_models):
+        raise _lib.KernelError(f"fedavg_exchange: {len(src_models)} sources but {len(weights)} weights")
+    if copy_only:
+        weights = [1.0] * len(src_models)
+    _fedavg_exchange_call("fedavg_exchange", src_models, weights, dst_models, table, [1 if copy_only else 0])
+
+
+def fedavg_exchange_counters(src_models, dst_models, table):
+    """The int64 max over the source models' segments into every destination model's."""
+    _fedavg_exchange_call("fedavg_exchange_counters", src_models, None, dst_models, table, [])
+
+
 # ------------------------------------------------------------------ clip input pipeline
 def frames_normalize(frames, mean, std, bgr_swap=True, valid=None, out=None):
     """uint8 [B,T,H,W,3] decoded frames -> fp32 [B,3,T,H,W] normalised clip

@@ -1280,6 +1280,40 @@ def fedavg_counters_max(bufs):
     return torch.ops.ssl_mae.fedavg_counters_max(list(bufs))
 
 
+FEDAVG_MAX_CLIENTS = _K.FEDAVG_MAX_CLIENTS
+fedavg_exchange_table = _K.fedavg_exchange_table     # host-side table build and upload, no launch
+
+
+# The exchange writes through the table's addresses: `tensors` names what those writes reach
+# (every destination model's segments), so the dispatcher sees the mutation.
+@_op("fedavg_exchange", "(Tensor(a!)[] tensors, int[] src_models, float[] weights, int[] dst_models, Tensor table, "
+                        "bool copy_only) -> ()", ("tensors",))
+def _fedavg_exchange(tensors, src_models, weights, dst_models, table, copy_only):
+    _K.fedavg_exchange(list(src_models), list(weights), list(dst_models), table, copy_only)
+
+
+_fedavg_exchange.register_fake(_none)
+
+
+def fedavg_exchange(tensors, src_models, weights, dst_models, table, copy_only=False):
+    torch.ops.ssl_mae.fedavg_exchange(list(tensors), [int(i) for i in src_models], [float(w) for w in weights],
+                                      [int(i) for i in dst_models], table, bool(copy_only))
+
+
+@_op("fedavg_exchange_counters", "(Tensor(a!)[] tensors, int[] src_models, int[] dst_models, Tensor table) -> ()",
+     ("tensors",))
+def _fedavg_exchange_counters(tensors, src_models, dst_models, table):
+    _K.fedavg_exchange_counters(list(src_models), list(dst_models), table)
+
+
+_fedavg_exchange_counters.register_fake(_none)
+
+
+def fedavg_exchange_counters(tensors, src_models, dst_models, table):
+    torch.ops.ssl_mae.fedavg_exchange_counters(list(tensors), [int(i) for i in src_models],
+                                               [int(i) for i in dst_models], table)
+
+
 @_op("frames_normalize", "(Tensor frames, float[] mean, float[] std, bool bgr_swap, Tensor? valid) -> Tensor")
 def _frames_normalize(frames, mean, std, bgr_swap, valid):
     return _K.frames_normalize(frames, mean, std, bgr_swap, valid)

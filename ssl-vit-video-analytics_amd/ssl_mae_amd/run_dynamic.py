@@ -84,10 +84,11 @@ class SyntheticLoader:
         return iter(self.batches)
 
 
-def split_loader(cfg, device):
+def split_loader(cfg, device, shuffle=False, drop_last=False, seed=None):
     """`dataset.split`: lines of `<frame directory> <label>`; frames decoded on the host at
     their own size, resized to `image_size` and normalised on the device
-    (mae_loader.ClipResizer)."""
+    (mae_loader.ClipResizer).  `shuffle` / `drop_last` (training loaders) draw their order
+    from a generator seeded with `seed`."""
     from .mae_loader import ClipResizer, LazyVideoMAEDataset, collate_raw
     ds, rt = cfg["dataset"], cfg["runtime"]
     data = LazyVideoMAEDataset(ds["split"], clip_len=int(ds["clip_len"]), stride=int(ds["stride"]),
@@ -107,7 +108,9 @@ def split_loader(cfg, device):
     def collate(batch):
         return collate_raw([b[:2] for b in batch]) + (torch.tensor([b[2] for b in batch]),)
 
-    loader = torch.utils.data.DataLoader(Labelled(), batch_size=int(rt["batch_size"]), shuffle=False,
+    gen = torch.Generator().manual_seed(int(seed)) if seed is not None else None
+    loader = torch.utils.data.DataLoader(Labelled(), batch_size=int(rt["batch_size"]), shuffle=bool(shuffle),
+                                         drop_last=bool(drop_last), generator=gen,
                                          num_workers=int(rt["num_workers"]), collate_fn=collate)
 
     class Normalised:

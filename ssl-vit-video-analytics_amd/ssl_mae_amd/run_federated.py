@@ -1,0 +1,441 @@
+"""Federated fine-tuning experiment, the reference's "system-level privacy" study
+(src/run_federated.py), MI355X-native: a centralized baseline, class-shard non-IID FedAvg over
+finetune.VideoClassifier models on one GPU, and a communication summary.
+
+    PYTHONPATH=ssl-vit-video-analytics_amd python -m ssl_mae_amd.run_federated \
+        --config configs/federated.yaml [--save_dir results/federated] [--exchange fused|reference]
+
+Flow (run_federated.py:209-363): centralized baseline -> client splits + fed_client_stats.csv ->
+global and client models -> FedAvg rounds -> fed_summary.csv, centralized_summary.csv and
+system_privacy_summary.csv, with the reference's columns and 6-decimal rounding.  The round's
+exchange goes through federated.run_fedavg_fused (one broadcast launch and one aggregation launch
+over the models' tensors where they live); `federated.exchange: reference` keeps run_fedavg's
+state_dict path, with bit-identical model states.
+
+`make_class_shard_splits` / `read_split` / `write_split` are src/datasets/federated_split.py
+(same random.Random(seed) call order: the same seed writes the same files), `client_update` is
+src/federated/client_sim.py under bf16 autocast with the cross-entropy from sm_logits_metrics,
+`evaluate_topk` is run_federated.py:20-39 through the same kernel.  Without `dataset.train_split`
+the driver runs on labelled synthetic clips, partitioned by the same class-shard rule.
+"""
+import argparse
+import csv
+import random
+from collections import defaultdict
+from pathlib import Path
+
+import torch
+
+from . import ops as K    # every kernel launch through the torch.ops.ssl_mae dispatcher
+from .federated import bytes_to_mb, run_fedavg, run_fedavg_fused
+from .finetune import VideoClassifier
+from .run_dynamic import load_finetune_ckpt, split_loader
+from .temporal_ssl import TopCEFn
+from .utils import load_config, set_seed
+
+CLIENT_STATS_HEADER = "client,num_samples,num_classes,classes\n"
+FED_COLUMNS = ("round", "val_top1", "val_top5", "avg_local_loss", "clients", "model_mb", "comm_mb_round",
+               "comm_mb_total")
+CENTRALIZED_COLUMNS = ("epoch", "train_loss", "val_top1", "val_top5")
+SYSTEM_COLUMNS = ("raw_upload_mb_est", "fed_comm_total_mb", "reduction_ratio")
+EXCHANGES = {"fused": run_fedavg_fused, "reference": run_fedavg}
+
+DEFAULTS = {
+    "dataset": {"name": None, "train_split": None, "val_split": None, "num_classes": 101, "clip_len": 16,
+                "stride": 4, "image_size": 112},
+    "model": {"embed_dim": 576, "init_ckpt": None},
+    "federated": {"num_clients": 4, "rounds": 3, "local_epochs": 1, "client_fraction": 1.0, "batch_size": 8,
+                  "lr": 3e-4, "weight_decay": 0.01, "exchange": "fused",
+                  "non_iid": {"enabled": True, "strategy": "class_shard", "shards_per_client": 6,
+                              "min_samples_per_client": 200}},
+    # None: the federated value (epochs: rounds * local_epochs, the same training budget)
+    "centralized": {"enabled": True, "epochs": None, "batch_size": None, "lr": None, "weight_decay": None},
+    "system_privacy": {"estimate_raw_upload": True, "raw_dtype_bytes": 1},
+    "synthetic": {"num_train": 96, "num_val": 32},
+    "runtime": {"amp": True, "seed": 42, "num_workers": 4},
+    "output": {"save_dir": "results/federated", "split_prefix": "fed"},
+}
+
+
+def resolve_config(cfg, save_dir=None, exchange=None):
+    """The file's values over DEFAULTS, the command line over both; unknown sections or keys
+    raise, and so does `non_iid.enabled: false` (run_federated.py:263-264)."""
+    out = {sec: dict(vals) for sec, vals in DEFAULTS.items()}
+    out["federated"]["non_iid"] = dict(DEFAULTS["federated"]["non_iid"])
+    for sec, vals in (cfg or {}).items():
+        if sec not in out:
+            raise ValueError(f"[ERROR] Unknown config section: {sec}")
+        vals = dict(vals or {})
+        unknown = set(vals) - set(out[sec])
+        if unknown:
+            raise ValueError(f"[ERROR] Unknown keys in {sec}: {sorted(unknown)}")
+        if sec == "federated" and "non_iid" in vals:
+            non_iid = dict(vals.pop("non_iid") or {})
+            unknown = set(non_iid) - set(out[sec]["non_iid"])
+            if unknown:
+                raise ValueError(f"[ERROR] Unknown keys in federated.non_iid: {sorted(unknown)}")
+            out[sec]["non_iid"].update(non_iid)
+        out[sec].update(vals)
+    if save_dir is not None:
+        out["output"]["save_dir"] = save_dir
+    if exchange is not None:
+        out["federated"]["exchange"] = exchange
+    fed = out["federated"]
+    if fed["exchange"] not in EXCHANGES:
+        raise ValueError(f"[ERROR] Unknown federated.exchange: {fed['exchange']}, must be one of {sorted(EXCHANGES)}")
+    if not fed["non_iid"]["enabled"]:
+        raise RuntimeError("[ERROR] IID mode not implemented; enable non_iid.")
+    if int(fed["num_clients"]) < 1 or int(fed["rounds"]) < 0 or int(fed["local_epochs"]) < 0 \
+            or int(fed["batch_size"]) < 1 or int(fed["non_iid"]["shards_per_client"]) < 1:
+        raise ValueError("[ERROR] federated: num_clients, batch_size, shards_per_client >= 1; rounds, "
+                         "local_epochs >= 0")
+    return out
+
+
+# ------------------------------------------------------------------ class-shard splits (federated_split.py)
+def read_split(split_file):
+    items = []
+    with open(split_file, "r", encoding="utf-8") as f:
+        for line in f:
+            line = line.strip()
+            if not line:
+                continue
+            p, y = line.split()
+            items.append((p, int(y)))
+    return items
+
+
+def write_split(items, out_path):
+    out_path = Path(out_path)
+    out_path.parent.mkdir(parents=True, exist_ok=True)
+    with open(out_path, "w", encoding="utf-8") as f:
+        for p, y in items:
+            f.write(f"{p} {y}\n")
+
+
+def shard_items(items, num_clients, shards_per_client=6, seed=42, min_samples_per_client=200):
+    """federated_split.py:43-86 on a list of (path, label): every class is one shard, shuffled
+    within; the shuffled class list is dealt out `shards_per_client` classes per client with
+    wrap-around; then up to 200 moves of at most 200 samples from the largest client to the
+    smallest while one is below `min_samples_per_client` (which can leave a client empty)."""
+    rng = random.Random(seed)
+    by_class = defaultdict(list)
+    for p, y in items:
+        by_class[y].append((p, y))
+    for y in by_class:
+        rng.shuffle(by_class[y])
+    class_ids = sorted(by_class.keys())
+    rng.shuffle(class_ids)
+    client_items = [[] for _ in range(num_clients)]
+    for idx, cid in enumerate(class_ids):
+        client_items[(idx // shards_per_client) % num_clients].extend(by_class[cid])
+    for _ in range(200):
+        s = [len(ci) for ci in client_items]
+        mn, mx = min(s), max(s)
+        if mn >= min_samples_per_client:
+            break
+        small, large = s.index(mn), s.index(mx)
+        if len(client_items[large]) <= min_samples_per_client:
+            break
+        move_n = min(200, len(client_items[large]) - min_samples_per_client)
+        client_items[small].extend(client_items[large][:move_n])
+        client_items[large] = client_items[large][move_n:]
+    return client_items
+
+
+def make_class_shard_splits(base_split_file, num_clients, shards_per_client=6, seed=42, min_samples_per_client=200,
+                            out_prefix="fed", out_dir="data/splits"):
+    """federated_split.py:26-105 -> (paths of {out_dir}/{out_prefix}_client_{i}_train.txt, stats)."""
+    client_items = shard_items(read_split(base_split_file), num_clients, shards_per_client, seed,
+                               min_samples_per_client)
+    out_paths, out_stats = [], []
+    for i, items in enumerate(client_items):
+        out_path = Path(out_dir) / f"{out_prefix}_client_{i}_train.txt"
+        write_split(items, out_path)
+        out_paths.append(str(out_path))
+        cls_set = sorted({y for _, y in items})
+        out_stats.append({"client": i, "num_samples": len(items), "num_classes": len(cls_set),
+                          "classes": " ".join(map(str, cls_set[:50]))})
+    return out_paths, out_stats
+
+
+# ------------------------------------------------------------------ loaders
+class SyntheticClips:
+    """`n` labelled uniform-noise clips on the device (run_dynamic.SyntheticLoader's pixels), named
+    `synthetic/<index>` in split files so the class-shard rule partitions them like real ones."""
+
+    def __init__(self, cfg, n, seed, device):
+        ds = cfg["dataset"]
+        g = torch.Generator().manual_seed(int(seed))
+        T, S = int(ds["clip_len"]), int(ds["image_size"])
+        clips = (torch.rand(n, 3, T, S, S, generator=g) - 0.45) / 0.226 * (0.3 + 1.4 * torch.rand(n, 1, T, 1, 1, generator=g))
+        self.clips = clips.to(device)
+        self.labels = torch.randint(0, int(ds["num_classes"]), (n,), generator=g)
+
+    def items(self):
+        return [(f"synthetic/{i}", int(y)) for i, y in enumerate(self.labels.tolist())]
+
+    def loader(self, items, batch_size, shuffle, seed):
+        idx = torch.tensor([int(p.split("/")[1]) for p, _ in items], dtype=torch.long)
+        return _SyntheticLoader(self, idx, int(batch_size), bool(shuffle), int(seed))
+
+
+class _SyntheticLoader:
+    """Batches of a SyntheticClips subset; shuffle implies drop_last (utils_fed.build_loader)
+    and a fresh permutation per pass from one seeded generator."""
+
+    def __init__(self, data, idx, batch_size, shuffle, seed):
+        self.data, self.idx, self.batch_size, self.shuffle = data, idx, batch_size, shuffle
+        self.gen = torch.Generator().manual_seed(seed)
+
+    def __len__(self):
+        n = len(self.idx)
+        return n // self.batch_size if self.shuffle else (n + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        idx = self.idx[torch.randperm(len(self.idx), generator=self.gen)] if self.shuffle else self.idx
+        labels = self.data.labels.to(self.data.clips.device)
+        for b in range(len(self)):
+            sel = idx[b * self.batch_size:(b + 1) * self.batch_size].to(self.data.clips.device)
+            yield self.data.clips[sel], labels[sel]
+
+
+def _split_file_loader(cfg, split_file, batch_size, shuffle, seed, device):
+    shim = {"dataset": dict(cfg["dataset"], split=str(split_file)),
+            "runtime": {"batch_size": int(batch_size), "num_workers": cfg["runtime"]["num_workers"]}}
+    return split_loader(shim, device, shuffle=shuffle, drop_last=shuffle, seed=seed)
+
+
+# ------------------------------------------------------------------ client update / evaluation
+def _train_pass(model, loader, opt, device, amp, loss_sum):
+    """One pass over `loader` (client_sim.py:45-65); adds loss * batch to the device scalar
+    `loss_sum` and returns the number of samples."""
+    total = 0
+    for clip, y in loader:
+        clip = clip.to(device, non_blocking=True)
+        y = y.to(device, non_blocking=True).long()
+        opt.zero_grad(set_to_none=True)
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bool(amp)):
+            logits = model(clip)
+        loss = TopCEFn.apply(logits, y)
+        loss.backward()
+        opt.step()
+        bs = int(y.size(0))
+        loss_sum += loss.detach().double() * bs
+        total += bs
+    return total
+
+
+def client_update(model, loader, device, epochs=1, lr=3e-4, weight_decay=0.01, amp=True):
+    """client_sim.py:30-67: `epochs` local passes with a fresh AdamW over all parameters; returns
+    the average loss.  The running loss * batch sum stays on the device: one read-back per call."""
+    model.train()
+    opt = torch.optim.AdamW(model.parameters(), lr=float(lr), weight_decay=float(weight_decay))
+    loss_sum = torch.zeros((), dtype=torch.float64, device=device)
+    total = 0
+    for _ in range(int(epochs)):
+        total += _train_pass(model, loader, opt, device, amp, loss_sum)
+    return float(loss_sum.item()) / max(1, total)
+
+
+@torch.no_grad()
+def evaluate_topk(model, loader, device):
+    """run_federated.py:20-39 -> (top1, top5) with k = min(5, classes), counted by
+    sm_logits_metrics (its tie rule: kernels.logits_metrics) and read back once."""
+    model.eval()
+    hits = torch.zeros(2, dtype=torch.float64, device=device)
+    total = 0
+    for clip, y in loader:
+        clip = clip.to(device, non_blocking=True)
+        y = y.to(device, non_blocking=True).long()
+        logits = model(clip).float().contiguous()
+        hits += K.logits_metrics(logits, y, min(5, logits.shape[1]))[0, 2:4]
+        total += int(y.size(0))
+    top1, top5 = hits.cpu().tolist()
+    return top1 / max(1, total), top5 / max(1, total)
+
+
+def _write_csv(path, header, rows):
+    """utils.write_csv of the reference."""
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "w", encoding="utf-8", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=list(header))
+        w.writeheader()
+        for r in rows:
+            w.writerow(r)
+
+
+def _new_model(cfg, device):
+    model = VideoClassifier(int(cfg["dataset"]["num_classes"]), embed_dim=int(cfg["model"]["embed_dim"]),
+                            img_size=int(cfg["dataset"]["image_size"]))
+    load_finetune_ckpt(model, cfg["model"]["init_ckpt"])
+    return model.to(device)
+
+
+def train_centralized(cfg, device, train_loader, val_loader, out_dir, log=print):
+    """run_federated.py:100-180: the baseline under the same budget, epochs = rounds *
+    local_epochs unless overridden, one AdamW across all epochs.  `train_loader(batch_size)`
+    builds the shuffled loader over the whole training split.  Returns the rows of
+    centralized_summary.csv, or None when disabled."""
+    c_cfg, fed = cfg["centralized"], cfg["federated"]
+    if not bool(c_cfg["enabled"]):
+        return None
+    epochs = c_cfg["epochs"]
+    epochs = int(fed["rounds"]) * int(fed["local_epochs"]) if epochs is None else int(epochs)
+
+    def pick(key):
+        return fed[key] if c_cfg[key] is None else c_cfg[key]
+
+    loader = train_loader(int(pick("batch_size")))
+    model = _new_model(cfg, device)
+    model.train()
+    opt = torch.optim.AdamW(model.parameters(), lr=float(pick("lr")), weight_decay=float(pick("weight_decay")))
+    rows = []
+    for ep in range(1, epochs + 1):
+        model.train()
+        loss_sum = torch.zeros((), dtype=torch.float64, device=device)
+        total = _train_pass(model, loader, opt, device, cfg["runtime"]["amp"], loss_sum)
+        avg_loss = float(loss_sum.item()) / max(1, total)
+        top1, top5 = evaluate_topk(model, val_loader, device)
+        log(f"[INFO][Centralized] ep={ep}/{epochs} train_loss={avg_loss:.4f} val_top1={top1:.4f} "
+            f"val_top5={top5:.4f}")
+        rows.append({"epoch": ep, "train_loss": round(avg_loss, 6), "val_top1": round(top1, 6),
+                     "val_top5": round(top5, 6)})
+    out_csv = Path(out_dir) / "centralized_summary.csv"
+    _write_csv(out_csv, CENTRALIZED_COLUMNS, rows)
+    log(f"[INFO] Saved centralized summary: {out_csv}")
+    return rows
+
+
+def estimate_raw_upload_mb(cfg, train_split):
+    """run_federated.py:183-206: the MiB a centralized run would upload once, samples x
+    3 x clip_len x image_size^2 x raw_dtype_bytes; None when switched off."""
+    sp = cfg["system_privacy"]
+    if not bool(sp["estimate_raw_upload"]):
+        return None
+    clip_len, img = int(cfg["dataset"]["clip_len"]), int(cfg["dataset"]["image_size"])
+    per_sample_bytes = 3 * clip_len * img * img * int(sp["raw_dtype_bytes"])
+    with open(train_split, "r", encoding="utf-8") as f:
+        n = sum(1 for line in f if line.strip())
+    return bytes_to_mb(n * per_sample_bytes)
+
+
+def fed_summary_rows(records):
+    """run_federated.py:328-341 -> (rows of fed_summary.csv, total communication in MiB)."""
+    comm_total, rows = 0.0, []
+    for r in records:
+        comm_total += float(r["comm_mb_round"])
+        rows.append({"round": r["round"], "val_top1": round(float(r["val_top1"]), 6),
+                     "val_top5": round(float(r["val_top5"]), 6),
+                     "avg_local_loss": round(float(r["avg_local_loss"]), 6), "clients": int(r["clients"]),
+                     "model_mb": round(float(r["model_mb"]), 6),
+                     "comm_mb_round": round(float(r["comm_mb_round"]), 6),
+                     "comm_mb_total": round(float(comm_total), 6)})
+    return rows, comm_total
+
+
+def system_privacy_row(raw_upload_mb, fed_comm_mb):
+    """run_federated.py:356-360."""
+    has_raw = raw_upload_mb is not None
+    return {"raw_upload_mb_est": round(raw_upload_mb, 6) if has_raw else "",
+            "fed_comm_total_mb": round(fed_comm_mb, 6),
+            "reduction_ratio": round(fed_comm_mb / raw_upload_mb, 6) if has_raw and raw_upload_mb > 0 else ""}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Federated fine-tuning: centralized baseline, non-IID FedAvg, "
+                                             "communication summary.")
+    ap.add_argument("--config", default="configs/federated.yaml")
+    ap.add_argument("--save_dir", default=None, help="override output.save_dir")
+    ap.add_argument("--exchange", default=None, help="override federated.exchange (fused|reference)")
+    args = ap.parse_args(argv)
+    cfg = resolve_config(load_config(args.config), args.save_dir, args.exchange)
+    seed = int(cfg["runtime"]["seed"])
+    set_seed(seed)
+    if not torch.cuda.is_available():
+        raise RuntimeError("[ERROR] run_federated needs an MI355X: the HIP kernels have no CPU fallback")
+    device = torch.device("cuda")
+    from .build import build
+    build()
+    fed, ds = cfg["federated"], cfg["dataset"]
+    out_dir = Path(cfg["output"]["save_dir"])
+    out_dir.mkdir(parents=True, exist_ok=True)
+    batch_size = int(fed["batch_size"])
+
+    if ds["train_split"]:
+        if not ds["val_split"]:
+            raise ValueError("[ERROR] dataset.val_split is needed with dataset.train_split")
+        train_split, split_dir = Path(ds["train_split"]), Path(ds["train_split"]).parent
+
+        def loader_of(split_file, bs, shuffle, s):
+            return _split_file_loader(cfg, split_file, bs, shuffle, s, device)
+    else:
+        # labelled synthetic clips, listed in a split file so the same class-shard rule applies
+        split_dir = out_dir / "splits"
+        train_split = split_dir / "synthetic_train.txt"
+        train_set = SyntheticClips(cfg, int(cfg["synthetic"]["num_train"]), seed, device)
+        val_set = SyntheticClips(cfg, int(cfg["synthetic"]["num_val"]), seed + 1, device)
+        write_split(train_set.items(), train_split)
+        write_split(val_set.items(), split_dir / "synthetic_val.txt")
+
+        def loader_of(split_file, bs, shuffle, s):
+            data = val_set if Path(split_file).name == "synthetic_val.txt" else train_set
+            return data.loader(read_split(split_file), bs, shuffle, s)
+    val_split = Path(ds["val_split"]) if ds["train_split"] else split_dir / "synthetic_val.txt"
+
+    with open(out_dir / "federated.log", "a", encoding="utf-8") as log_f:
+        def log(msg):
+            print(msg)
+            log_f.write(msg + "\n")
+            log_f.flush()
+
+        log(f"[INFO] Federated experiment started, exchange={fed['exchange']}")
+        val_loader = loader_of(val_split, batch_size, False, seed + 999)
+        centralized_rows = train_centralized(cfg, device, lambda bs: loader_of(train_split, bs, True, seed + 123),
+                                             val_loader, out_dir, log)
+
+        num_clients = int(fed["num_clients"])
+        split_paths, client_stats = make_class_shard_splits(
+            str(train_split), num_clients, shards_per_client=int(fed["non_iid"]["shards_per_client"]), seed=seed,
+            min_samples_per_client=int(fed["non_iid"]["min_samples_per_client"]),
+            out_prefix=cfg["output"]["split_prefix"], out_dir=str(split_dir))
+        stats_csv = out_dir / "fed_client_stats.csv"
+        stats_csv.write_text(CLIENT_STATS_HEADER + "".join(
+            f"{s['client']},{s['num_samples']},{s['num_classes']},{s['classes']}\n" for s in client_stats),
+            encoding="utf-8")
+        log(f"[INFO] Saved client stats: {stats_csv}")
+
+        global_model = _new_model(cfg, device)
+        client_models = [VideoClassifier(int(ds["num_classes"]), embed_dim=int(cfg["model"]["embed_dim"]),
+                                         img_size=int(ds["image_size"])).to(device) for _ in range(num_clients)]
+        client_sizes, client_loaders = [], []
+        for cid in range(num_clients):
+            loader = loader_of(split_paths[cid], batch_size, True, seed + cid)
+            client_sizes.append(client_stats[cid]["num_samples"])
+
+            def update_fn(model, _loader=loader):
+                return client_update(model, _loader, device, epochs=int(fed["local_epochs"]), lr=float(fed["lr"]),
+                                     weight_decay=float(fed["weight_decay"]), amp=bool(cfg["runtime"]["amp"]))
+
+            client_loaders.append({"loader": loader, "update_fn": update_fn})
+
+        records = EXCHANGES[fed["exchange"]](
+            global_model, client_models, client_loaders, client_sizes, lambda m: evaluate_topk(m, val_loader, device),
+            device, rounds=int(fed["rounds"]), client_fraction=float(fed["client_fraction"]),
+            amp=bool(cfg["runtime"]["amp"]), log_f=log_f)
+
+        rows, comm_total = fed_summary_rows(records)
+        fed_csv = out_dir / "fed_summary.csv"
+        _write_csv(fed_csv, FED_COLUMNS, rows)
+        log(f"[INFO] Saved federated summary: {fed_csv}")
+        sys_row = system_privacy_row(estimate_raw_upload_mb(cfg, train_split), comm_total)
+        sys_csv = out_dir / "system_privacy_summary.csv"
+        _write_csv(sys_csv, SYSTEM_COLUMNS, [sys_row])
+        log(f"[INFO] Saved system privacy summary: {sys_csv}")
+    return {"centralized": centralized_rows, "federated": rows, "system": sys_row, "client_stats": client_stats,
+            "save_dir": out_dir}
+
+
+if __name__ == "__main__":
+    main()
