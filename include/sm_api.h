@@ -521,6 +521,53 @@ int sm_adamw(float* p, const float* g, float* m, float* v, void* bf16_shadow, in
              float b1, float b2, float eps, float wd, const int* found_inf, int64_t* step,
              int advance_step, hipStream_t st);
 
+/* ---- grouped AdamW: one launch updates any number of fp32 ranges, each with the learning rate
+ * and weight decay of its parameter group (fine-tuning with a head / backbone learning rate,
+ * layer-wise learning-rate decay, no decay on biases and norms).
+ *
+ * AdamW segment table (DEVICE memory, 16-byte aligned, built once per set of S segments; a
+ * segment is one contiguous fp32 range with its gradient and its two moment ranges):
+ *   SmAdamwTableHeader                     64 bytes
+ *   uint64_t addr[4][S]                    device addresses of segment s: row 0 the parameters,
+ *                                          1 the gradients, 2 exp_avg, 3 exp_avg_sq; each a
+ *                                          multiple of 4, not necessarily of 16
+ *   int64_t  seg_len[S]                    elements (0 allowed: such a segment has no chunk)
+ *   int64_t  chunk_off[C]                  first element of the chunk within its segment,
+ *                                          a multiple of SM_ADAMW_CHUNK_ELEMS
+ *   int32_t  chunk_seg[C]                  the chunk's segment; a chunk covers
+ *                                          min(SM_ADAMW_CHUNK_ELEMS, seg_len - chunk_off) elements
+ *   int32_t  seg_group[S]                  the segment's parameter group
+ *   zero padding to a multiple of 16 bytes
+ * total_bytes = 64 + 44 S + 12 C rounded up to 16.  The chunks together cover every element of
+ * every segment once.
+ *
+ * sm_adamw_table: sm_adamw's update (the same device function, bit for bit) of every element of
+ * every segment, segment s with fp32(lr[seg_group[s]] * lr_mult) and wd[seg_group[s]]; lr and wd
+ * are HOST arrays of num_groups (1..SM_ADAMW_MAX_GROUPS) floats, passed to the kernel by value.
+ * check_finite != 0: *found_inf is reset, then set to 1 when any gradient element of any segment
+ * is not finite; the update then writes nothing and *step keeps its value.  Otherwise every
+ * segment is updated at step *step + 1 and *step advances once.  check_finite == 0: found_inf is
+ * neither read nor written (may be NULL).  At most three operations are enqueued on the stream
+ * (the flag's reset, the flag pass, the update pass) and the host is never synchronised: the
+ * header was validated when the table was built and is not read back (the kernels compare its
+ * magic and counts with the arguments and touch nothing on a mismatch).  A chunk moves as 16-byte
+ * vectors when its four bases are 16-byte aligned, else element by element; each segment's
+ * len % 4 tail is scalar; the update is element-wise, so both forms give the same bits.  No
+ * atomics in the update pass.
+ * Returns -2, with nothing launched, for a NULL table, lr, wd, step (or found_inf with
+ * check_finite), a table that is not 16-byte aligned, negative counts, num_groups outside
+ * 1..SM_ADAMW_MAX_GROUPS or a table_bytes that is not the formula's value for the counts; 0, with
+ * nothing launched, for zero segments (or zero chunks). */
+#define SM_ADAMW_MAX_GROUPS 64
+#define SM_ADAMW_CHUNK_ELEMS 2048
+#define SM_ADAMW_TABLE_MAGIC 0x314254574D414441LL /* "ADAMWTB1" */
+typedef struct SmAdamwTableHeader {
+  int64_t magic, num_segments, num_chunks, chunk_elems, total_bytes, reserved[3];
+} SmAdamwTableHeader;
+int sm_adamw_table(const void* table, int64_t table_bytes, int64_t num_segments, int64_t num_chunks,
+                   int num_groups, const float* lr, const float* wd, float lr_mult, float b1, float b2,
+                   float eps, int* found_inf, int64_t* step, int check_finite, hipStream_t st);
+
 /* ---- temporal SSL pretraining (src/train_ssl.py; csrc/temporal.hip).  No atomics: every
  * reduction has a fixed partition and order, results are bitwise reproducible.
  *

@@ -13,6 +13,9 @@
 //  * AdamW (torch.optim.AdamW semantics) over one flat fp32 parameter buffer with
 //    a GradScaler-style non-finite check (step skipped on inf/nan, no host sync),
 //    refreshing the bf16 weight shadow in the same pass.
+//  * grouped AdamW over a device table of segments (sm_adamw_table): the same per-element
+//    update for any number of fp32 ranges, each with its parameter group's learning rate and
+//    weight decay, in one launch (plus the flag pass).
 #include "common.h"
 #include "sm_api.h"
 
@@ -268,21 +271,38 @@ __global__ void nonfinite_kernel(const float* g, int64_t n, int* flag) {
   if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
 }
 
+// What every element of a step shares: torch.optim.AdamW's bias corrections at step t (fp64,
+// rounded once) and the products of the hyperparameters.
+struct AdamwCoef {
+  float decay, one_minus_b1, b2, one_minus_b2, bc2s, eps, step_size;
+};
+
+SM_DEV float2 adamw_bias_corrections(float b1, float b2, int64_t t_step) {
+  const double t = (double)t_step;
+  return make_float2((float)(1.0 - pow((double)b1, t)), (float)sqrt(1.0 - pow((double)b2, t)));
+}
+
+SM_DEV AdamwCoef adamw_coef(float lr, float b1, float b2, float eps, float wd, float2 bc) {
+  return AdamwCoef{fmaf(-lr, wd, 1.f), 1.f - b1, b2, 1.f - b2, bc.y, eps, lr / bc.x};
+}
+
+// The update of one element, shared by adamw_kernel and adamw_table_kernel.  The three fused
+// multiply-adds are written out (they are the ones -ffp-contract=fast formed from the plain
+// expressions), so the bits do not depend on what surrounds the call.
+SM_DEV void adamw_update(const AdamwCoef& c, float& p, float g, float& m, float& v) {
+  m = fmaf(c.one_minus_b1, g - m, m);
+  v = fmaf(c.one_minus_b2 * g, g, v * c.b2);
+  const float denom = sqrtf(v) / c.bc2s + c.eps;
+  p = fmaf(p, c.decay, -(c.step_size * (m / denom)));
+}
+
 __global__ void adamw_kernel(float* p, const float* g, float* m, float* v, __bf16* shadow, int64_t n, float lr,
                              float b1, float b2, float eps, float wd, const int* flag, const int64_t* step) {
   if (flag && *flag) return;
-  const double t = (double)(*step + 1);
-  const float bc1 = (float)(1.0 - pow((double)b1, t));
-  const float bc2s = (float)sqrt(1.0 - pow((double)b2, t));
-  const float step_size = lr / bc1;
+  const AdamwCoef c = adamw_coef(lr, b1, b2, eps, wd, adamw_bias_corrections(b1, b2, *step + 1));
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    float pv = p[i] * (1.f - lr * wd);
-    const float gv = g[i];
-    float mv = m[i];
-    mv = mv + (1.f - b1) * (gv - mv);
-    const float vv = v[i] * b2 + (1.f - b2) * gv * gv;
-    const float denom = sqrtf(vv) / bc2s + eps;
-    pv = pv - step_size * (mv / denom);
+    float pv = p[i], mv = m[i], vv = v[i];
+    adamw_update(c, pv, g[i], mv, vv);
     p[i] = pv;
     m[i] = mv;
     v[i] = vv;
@@ -292,6 +312,161 @@ __global__ void adamw_kernel(float* p, const float* g, float* m, float* v, __bf1
 
 __global__ void step_incr_kernel(const int* flag, int64_t* step) {
   if (!(flag && *flag)) *step += 1;
+}
+
+// ---- grouped AdamW over a segment table (sm_api.h "AdamW segment table"): one launch updates
+// every segment, each with its group's learning rate and weight decay.  A block takes whole
+// chunks, grid-stride; a lane owns elements tid + 256 u of the chunk's float4 groups (or of its
+// elements, in the scalar form) and the update is element-wise, so both forms give the same bits.
+constexpr int kAdamwChunk = SM_ADAMW_CHUNK_ELEMS;
+constexpr int kAdamwVec = kAdamwChunk / (256 * 4);   // float4 groups per lane per role
+static_assert(kAdamwChunk % 1024 == 0, "a chunk is a whole number of 256-lane float4 rows");
+constexpr int kAdamwMaxBlocks = 7 * 256;   // persistent grid: 7 resident 256-lane blocks on each of 256 CUs
+
+struct AdamwGroups {
+  float lr[SM_ADAMW_MAX_GROUPS];   // already multiplied by lr_mult
+  float wd[SM_ADAMW_MAX_GROUPS];
+};
+
+struct AdamwTableView {
+  int64_t S, C;
+  const uint64_t* addr;      // [4][S]: p, g, m, v
+  const int64_t* seg_len;    // [S]
+  const int64_t* chunk_off;  // [C]
+  const int32_t* chunk_seg;  // [C]
+  const int32_t* seg_group;  // [S]
+};
+
+// False when the header is not the one the call's counts describe (nothing is touched then).
+SM_DEV bool adamw_table_view(const unsigned char* tab, int64_t S, int64_t C, AdamwTableView& t) {
+  const SmAdamwTableHeader* h = (const SmAdamwTableHeader*)tab;
+  if (h->magic != SM_ADAMW_TABLE_MAGIC || h->num_segments != S || h->num_chunks != C ||
+      h->chunk_elems != kAdamwChunk)
+    return false;
+  t.S = S;
+  t.C = C;
+  t.addr = (const uint64_t*)(tab + sizeof(SmAdamwTableHeader));
+  t.seg_len = (const int64_t*)(t.addr + 4 * S);
+  t.chunk_off = t.seg_len + S;
+  t.chunk_seg = (const int32_t*)(t.chunk_off + C);
+  t.seg_group = t.chunk_seg + C;
+  return true;
+}
+
+// Elements [off, off + n) of segment `seg` (wave-uniform); false when the entry points outside it.
+SM_DEV bool adamw_chunk_range(const AdamwTableView& t, int64_t c, int& seg, int64_t& off, int64_t& n) {
+  seg = __builtin_amdgcn_readfirstlane(t.chunk_seg[c]);
+  off = t.chunk_off[c];
+  if (seg < 0 || seg >= t.S || off < 0) return false;
+  const int64_t len = t.seg_len[seg];
+  if (off >= len) return false;
+  n = len - off < kAdamwChunk ? len - off : kAdamwChunk;
+  return true;
+}
+
+// Flag pass: ORs 1 into *flag when any gradient element is not finite, and advances *step for the
+// update pass that follows (which takes it back when the flag is set).  flag == nullptr: only the
+// step.
+__global__ void __launch_bounds__(256) adamw_table_nonfinite_kernel(const unsigned char* tab, int64_t S, int64_t C,
+                                                                    int* flag, int64_t* step) {
+  AdamwTableView t;
+  if (!adamw_table_view(tab, S, C, t)) return;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *step += 1;
+  if (!flag) return;
+  const int tid = threadIdx.x;
+  int bad = 0;
+  for (int64_t c = blockIdx.x; c < C; c += gridDim.x) {
+    int seg;
+    int64_t off, n;
+    if (!adamw_chunk_range(t, c, seg, off, n)) continue;
+    const float* g = (const float*)t.addr[1 * S + seg] + off;
+    if (((uintptr_t)g & 15u) != 0) {
+      for (int64_t i = tid; i < n; i += 256) bad |= !isfinite(g[i]);
+      continue;
+    }
+    const int64_t n4 = n / 4;
+#pragma unroll
+    for (int u = 0; u < kAdamwVec; ++u)
+      if (tid + 256 * u < n4) {
+        const f32x4 x = __builtin_nontemporal_load((const f32x4*)g + tid + 256 * u);
+        bad |= !isfinite(x[0]) | !isfinite(x[1]) | !isfinite(x[2]) | !isfinite(x[3]);
+      }
+    if (n4 * 4 + tid < n) bad |= !isfinite(g[n4 * 4 + tid]);
+  }
+  if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
+}
+
+// 72 VGPRs (8 float4 loads in flight per lane), no scratch: 7 blocks resident per CU -- the
+// grid's size (kAdamwMaxBlocks); capping it at 64 VGPRs for an 8th block spills.
+__global__ void __launch_bounds__(256) adamw_table_kernel(AdamwGroups a, int num_groups, const unsigned char* tab,
+                                                          int64_t S, int64_t C, float b1, float b2, float eps,
+                                                          const int* flag, int64_t* step) {
+  AdamwTableView t;
+  if (!adamw_table_view(tab, S, C, t)) return;
+  if (flag && *flag) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *step -= 1;   // the skipped step does not count
+    return;
+  }
+  // *step was advanced by the pass before this one and nothing in this launch writes it
+  const float2 bc = adamw_bias_corrections(b1, b2, *step);
+  const int tid = threadIdx.x;
+  for (int64_t c = blockIdx.x; c < C; c += gridDim.x) {
+    int seg;
+    int64_t off, n;
+    if (!adamw_chunk_range(t, c, seg, off, n)) continue;
+    const int grp = __builtin_amdgcn_readfirstlane(t.seg_group[seg]);
+    if (grp < 0 || grp >= num_groups) continue;
+    const AdamwCoef k = adamw_coef(a.lr[grp], b1, b2, eps, a.wd[grp], bc);
+    float* p = (float*)t.addr[0 * S + seg] + off;
+    const float* g = (const float*)t.addr[1 * S + seg] + off;
+    float* m = (float*)t.addr[2 * S + seg] + off;
+    float* v = (float*)t.addr[3 * S + seg] + off;
+    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15u) != 0) {
+      for (int64_t i = tid; i < n; i += 256) {
+        float pv = p[i], mv = m[i], vv = v[i];
+        adamw_update(k, pv, g[i], mv, vv);
+        p[i] = pv;
+        m[i] = mv;
+        v[i] = vv;
+      }
+      continue;
+    }
+    const int64_t n4 = n / 4;
+    f32x4 pv[kAdamwVec], gv[kAdamwVec], mv[kAdamwVec], vv[kAdamwVec];
+#pragma unroll
+    for (int u = 0; u < kAdamwVec; ++u) {
+      const bool on = tid + 256 * u < n4;
+      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+      pv[u] = on ? __builtin_nontemporal_load((const f32x4*)p + tid + 256 * u) : z;
+      gv[u] = on ? __builtin_nontemporal_load((const f32x4*)g + tid + 256 * u) : z;
+      mv[u] = on ? __builtin_nontemporal_load((const f32x4*)m + tid + 256 * u) : z;
+      vv[u] = on ? __builtin_nontemporal_load((const f32x4*)v + tid + 256 * u) : z;
+    }
+    // the segment's scalar tail (n % 4 elements, last chunk only)
+    const int64_t ti = n4 * 4 + tid;
+    if (ti < n) {
+      float ps = p[ti], ms = m[ti], vs = v[ti];
+      adamw_update(k, ps, g[ti], ms, vs);
+      p[ti] = ps;
+      m[ti] = ms;
+      v[ti] = vs;
+    }
+#pragma unroll
+    for (int u = 0; u < kAdamwVec; ++u) {
+      if (tid + 256 * u >= n4) continue;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = pv[u][e], me = mv[u][e], ve = vv[u][e];
+        adamw_update(k, pe, gv[u][e], me, ve);
+        pv[u][e] = pe;
+        mv[u][e] = me;
+        vv[u][e] = ve;
+      }
+      __builtin_nontemporal_store(pv[u], (f32x4*)p + tid + 256 * u);
+      __builtin_nontemporal_store(mv[u], (f32x4*)m + tid + 256 * u);
+      __builtin_nontemporal_store(vv[u], (f32x4*)v + tid + 256 * u);
+    }
+  }
 }
 
 __global__ void fill_kernel(float* p, int64_t n, float v) {
@@ -470,6 +645,36 @@ extern "C" int sm_adamw(float* p, const float* g, float* m, float* v, void* bf16
     hipLaunchKernelGGL(adamw_kernel, dim3(ew_blocks(n)), dim3(256), 0, st, p, g, m, v, (__bf16*)bf16_shadow, n, lr,
                        b1, b2, eps, wd, found_inf, step);
   if (advance_step) hipLaunchKernelGGL(step_incr_kernel, dim3(1), dim3(1), 0, st, found_inf, step);
+  SM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sm_adamw_table(const void* table, int64_t table_bytes, int64_t num_segments, int64_t num_chunks,
+                              int num_groups, const float* lr, const float* wd, float lr_mult, float b1, float b2,
+                              float eps, int* found_inf, int64_t* step, int check_finite, hipStream_t st) {
+  if (num_groups < 1 || num_groups > SM_ADAMW_MAX_GROUPS || !lr || !wd || !step) return -2;
+  if (check_finite && !found_inf) return -2;
+  if (num_segments < 0 || num_chunks < 0 || num_segments > (int64_t)1 << 31 || num_chunks > (int64_t)1 << 40) return -2;
+  if (num_segments == 0 && num_chunks != 0) return -2;
+  const int64_t bytes = ((int64_t)sizeof(SmAdamwTableHeader) + 44 * num_segments + 12 * num_chunks + 15) / 16 * 16;
+  if (!table || ((uintptr_t)table & 15u) != 0 || table_bytes != bytes) return -2;
+  if (num_chunks == 0) return 0;   // no segments, or only empty ones: nothing to launch
+  AdamwGroups a{};
+  for (int i = 0; i < num_groups; ++i) {
+    a.lr[i] = lr[i] * lr_mult;
+    a.wd[i] = wd[i];
+  }
+  const unsigned char* tab = (const unsigned char*)table;
+  const dim3 g((unsigned)(num_chunks < kAdamwMaxBlocks ? num_chunks : kAdamwMaxBlocks)), b(256);
+  int* flag = check_finite ? found_inf : nullptr;
+  if (flag) {
+    const hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), st);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(adamw_table_nonfinite_kernel, flag ? g : dim3(1), b, 0, st, tab, num_segments, num_chunks, flag,
+                     step);
+  hipLaunchKernelGGL(adamw_table_kernel, g, b, 0, st, a, num_groups, tab, num_segments, num_chunks, b1, b2, eps,
+                     (const int*)flag, step);
   SM_CHECK_LAUNCH();
   return 0;
 }

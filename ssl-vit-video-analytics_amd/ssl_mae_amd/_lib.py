@@ -143,6 +143,8 @@ _SIGS = {
     "sm_nonfinite": (_c_i32, [_c_p, _c_i64, _c_p, _c_p]),
     "sm_adamw": (_c_i32, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_f32, _c_f32, _c_f32, _c_f32, _c_f32, _c_p, _c_p,
                           _c_i32, _c_p]),
+    "sm_adamw_table": (_c_i32, [_c_p, _c_i64, _c_i64, _c_i64, _c_i32, _c_p, _c_p, _c_f32, _c_f32, _c_f32, _c_f32, _c_p,
+                                _c_p, _c_i32, _c_p]),
     "sm_fedavg_weighted_sum": (_c_i32, [_c_i32, _c_p, _c_p, _c_i64, _c_p, _c_p]),
     "sm_fedavg_counters_max": (_c_i32, [_c_i32, _c_p, _c_i64, _c_p, _c_p]),
     "sm_fedavg_exchange": (_c_i32, [_c_i32, _c_p, _c_p, _c_i32, _c_p, _c_p, _c_i64, _c_i32, _c_p]),

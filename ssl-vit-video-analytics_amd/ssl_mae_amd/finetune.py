@@ -240,6 +240,78 @@ def resolve_mode(ft_cfg, cli_mode):
     return mode
 
 
+def layer_ids(model):
+    """{parameter name: layer id} for layer-wise learning-rate decay over a VideoClassifier: the
+    stem (`backbone.patch_embed.*`) is layer 0, every entry of a stage's Sequential one layer
+    in forward order (1 .. L, L the number of stage entries), any other backbone parameter L,
+    the classifier L + 1."""
+    sizes = [len(stage) for stage in model.backbone.stages]
+    L = sum(sizes)
+    ids = {}
+    for name, _ in model.named_parameters():
+        parts = name.split(".")
+        if parts[0] == "classifier":
+            ids[name] = L + 1
+        elif parts[:2] == ["backbone", "patch_embed"]:
+            ids[name] = 0
+        elif parts[:2] == ["backbone", "stages"]:
+            ids[name] = 1 + sum(sizes[:int(parts[2])]) + int(parts[3])
+        else:
+            ids[name] = L
+    return ids
+
+
+def param_groups(model, ft_cfg, mode):
+    """Torch-style parameter groups over the trainable parameters: lr = base *
+    layer_decay^(L + 1 - layer id), base = head_lr / backbone_lr in two_stage mode and
+    learning_rate otherwise; weight_decay 0 for parameters with ndim <= 1 when
+    training.no_decay_1d.  Parameters with equal (lr, weight_decay) share a group, in order of
+    first appearance (the head first in two_stage mode); each group lists its `names`.  With
+    layer_decay 1.0 and no_decay_1d false the groups are build_optimizer's."""
+    tr = ft_cfg["training"]
+    wd = float(tr["weight_decay"])
+    decay = float(tr.get("layer_decay", 1.0))
+    no_decay_1d = bool(tr.get("no_decay_1d", False))
+    base = float(tr["learning_rate"])
+    head_lr = float(tr.get("head_lr", base)) if mode == "two_stage" else base
+    backbone_lr = float(tr.get("backbone_lr", base)) if mode == "two_stage" else base
+    ids = layer_ids(model)
+    top = max(ids.values())
+    named = list(model.named_parameters())
+    if mode == "two_stage":       # build_optimizer lists the head's group first
+        named = [np for np in named if np[0].startswith("classifier.")] + \
+                [np for np in named if not np[0].startswith("classifier.")]
+    groups = {}
+    for name, p in named:
+        if not p.requires_grad:
+            continue
+        lr = (head_lr if name.startswith("classifier.") else backbone_lr) * decay ** (top - ids[name])
+        key = (lr, 0.0 if no_decay_1d and p.ndim <= 1 else wd)
+        g = groups.setdefault(key, {"params": [], "names": [], "lr": key[0], "weight_decay": key[1]})
+        g["params"].append(p)
+        g["names"].append(name)
+    return list(groups.values())
+
+
+def epoch_lr_mult(epoch, ft_cfg):
+    """Multiplier of every group's learning rate in epoch `epoch` (0-based).  schedule
+    `constant`: 1.  `cosine`: linear warmup (epoch + 1) / warmup_epochs, then half a cosine from 1
+    at epoch warmup_epochs towards min_lr / learning_rate over the remaining epochs."""
+    import math
+    tr = ft_cfg["training"]
+    schedule = tr.get("schedule", "constant")
+    if schedule == "constant":
+        return 1.0
+    if schedule != "cosine":
+        raise ValueError(f"[ERROR] Unknown training.schedule={schedule}, must be constant or cosine")
+    warmup, total = int(tr.get("warmup_epochs", 0)), int(tr["epochs"])
+    if epoch < warmup:
+        return (epoch + 1) / warmup
+    floor = float(tr.get("min_lr", 0.0)) / float(tr["learning_rate"])
+    progress = (epoch - warmup) / max(1, total - warmup)
+    return floor + 0.5 * (1.0 - floor) * (1.0 + math.cos(math.pi * progress))
+
+
 def build_optimizer(ft_cfg, model, mode):
     """train_finetune.py:164-195 (torch.optim.AdamW over the trainable parameters;
     the backbone's parameters are views of its flat buffer, their .grad views of the

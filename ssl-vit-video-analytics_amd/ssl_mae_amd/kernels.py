@@ -935,6 +935,87 @@ def adamw(p, g, m, v, lr, b1, b2, eps, wd, found_inf, step, shadow=None, advance
          float(eps), float(wd), ptr(found_inf), ptr(step), 1 if advance_step else 0, stream())
 
 
+ADAMW_MAX_GROUPS = 64                        # SM_ADAMW_MAX_GROUPS
+ADAMW_CHUNK_ELEMS = 2048                     # SM_ADAMW_CHUNK_ELEMS
+ADAMW_TABLE_MAGIC = 0x314254574D414441       # SM_ADAMW_TABLE_MAGIC
+
+
+def adamw_table_bytes(num_segments, num_chunks):
+    return (64 + 44 * num_segments + 12 * num_chunks + 15) // 16 * 16
+
+
+def adamw_table_layout(addrs, lens, groups):
+    """The bytes of sm_adamw_table's segment table (include/sm_api.h "AdamW segment table") as
+    a uint8 NumPy array; pure host code.  addrs: per segment the (p, g, m, v) device addresses;
+    lens: elements per segment; groups: the parameter group of each segment."""
+    import numpy as np
+    S = len(lens)
+    if len(addrs) != S or len(groups) != S:
+        raise _lib.KernelError(f"adamw_table_layout: {len(addrs)} address rows, {S} lengths, {len(groups)} groups")
+    addr = np.array([tuple(int(x) for x in a) for a in addrs], dtype=np.uint64).reshape(S, 4)
+    seg_len = np.array([int(n) for n in lens], dtype=np.int64).reshape(S)
+    seg_group = np.array([int(g) for g in groups], dtype=np.int64).reshape(S)
+    if (seg_len < 0).any():
+        raise _lib.KernelError("adamw_table_layout: a segment length is negative")
+    if (seg_group < 0).any() or (seg_group >= ADAMW_MAX_GROUPS).any():
+        raise _lib.KernelError(f"adamw_table_layout: group indices are 0..{ADAMW_MAX_GROUPS - 1}")
+    if (addr % 4 != 0).any() or (addr[seg_len > 0] == 0).any():
+        raise _lib.KernelError("adamw_table_layout: every segment address is a non-null multiple of 4")
+    n_chunks = (seg_len + ADAMW_CHUNK_ELEMS - 1) // ADAMW_CHUNK_ELEMS
+    chunk_seg = np.repeat(np.arange(S, dtype=np.int32), n_chunks)
+    first_chunk = np.cumsum(n_chunks) - n_chunks
+    chunk_off = (np.arange(len(chunk_seg), dtype=np.int64) - np.repeat(first_chunk, n_chunks)) * ADAMW_CHUNK_ELEMS
+    C = len(chunk_seg)
+    total = adamw_table_bytes(S, C)
+    header = np.array([ADAMW_TABLE_MAGIC, S, C, ADAMW_CHUNK_ELEMS, total, 0, 0, 0], dtype=np.int64)
+    raw = b"".join(a.tobytes() for a in (header, np.ascontiguousarray(addr.T), seg_len, chunk_off.astype(np.int64),
+                                         chunk_seg.astype(np.int32), seg_group.astype(np.int32)))
+    raw += b"\0" * (total - len(raw))
+    return np.frombuffer(raw, dtype=np.uint8)
+
+
+def adamw_table_counts(layout):
+    """(num_segments, num_chunks) of a table's bytes, after checking its header against the
+    documented formula -- the validation the per-step call relies on."""
+    import numpy as np
+    raw = np.asarray(layout, dtype=np.uint8)
+    if raw.size < 64:
+        raise _lib.KernelError("adamw table: shorter than its header")
+    magic, S, C, chunk, total = (int(x) for x in np.frombuffer(raw[:40].tobytes(), dtype=np.int64))
+    if magic != ADAMW_TABLE_MAGIC or chunk != ADAMW_CHUNK_ELEMS or S < 0 or C < 0 \
+            or total != adamw_table_bytes(S, C) or total != raw.size:
+        raise _lib.KernelError("adamw table: the header does not describe these bytes")
+    return S, C
+
+
+def adamw_table(addrs, lens, groups, device):
+    """Builds and uploads the segment table: (uint8 device tensor, num_segments, num_chunks)."""
+    layout = adamw_table_layout(addrs, lens, groups)
+    S, C = adamw_table_counts(layout)
+    table = torch.from_numpy(layout.copy()).to(device)
+    if table.data_ptr() % 16:
+        raise _lib.KernelError("adamw_table: the device allocation is not 16-byte aligned")
+    return table, S, C
+
+
+def adamw_table_step(table, num_segments, num_chunks, lr, wd, lr_mult, b1, b2, eps, found_inf, step,
+                     check_finite=True):
+    """One optimizer step over every segment of the table: segment s with lr[group[s]] * lr_mult
+    and wd[group[s]].  At most three stream operations, no host synchronisation."""
+    import ctypes
+    _chk(table, found_inf, step)
+    if table.dtype != torch.uint8 or not table.is_contiguous():
+        raise _lib.KernelError("adamw_table_step: the table is a contiguous uint8 device tensor (adamw_table)")
+    if len(lr) != len(wd):
+        raise _lib.KernelError(f"adamw_table_step: {len(lr)} learning rates but {len(wd)} weight decays")
+    n = len(lr)
+    lrs = (ctypes.c_float * max(1, n))(*[float(x) for x in lr])
+    wds = (ctypes.c_float * max(1, n))(*[float(x) for x in wd])
+    call("sm_adamw_table", ptr(table), table.numel(), int(num_segments), int(num_chunks), n,
+         ctypes.cast(lrs, ctypes.c_void_p), ctypes.cast(wds, ctypes.c_void_p), float(lr_mult), float(b1), float(b2),
+         float(eps), ptr(found_inf), ptr(step), 1 if check_finite else 0, stream())
+
+
 # ------------------------------------------------------------------ federated averaging
 def fedavg_weighted_sum(bufs, weights, out=None):
     """out = sum_j bufs[j] * weights[j] in client order (fed_loop.py:46-49), bit-exact.

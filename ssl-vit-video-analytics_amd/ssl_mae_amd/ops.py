@@ -1255,6 +1255,33 @@ def adamw(p, g, m, v, lr, b1, b2, eps, wd, found_inf, step, shadow=None, advance
                             shadow, bool(advance_step))
 
 
+ADAMW_MAX_GROUPS = _K.ADAMW_MAX_GROUPS
+adamw_table_layout = _K.adamw_table_layout     # host-side: the table's bytes
+adamw_table = _K.adamw_table                   # host-side table build and upload, no launch
+
+
+# The step writes through the table's addresses: `tensors` names what those writes reach (the
+# parameter and moment buffers), so the dispatcher sees the mutation.  The operator carries the
+# C symbol's name (sm_adamw_table); its Python entry is adamw_table_step.
+@_op("adamw_table", "(Tensor(a!)[] tensors, Tensor table, int num_segments, int num_chunks, float[] lr, float[] wd, "
+                    "float lr_mult, float b1, float b2, float eps, Tensor(b!)? found_inf, Tensor(c!) step, "
+                    "bool check_finite) -> ()", ("tensors", "found_inf", "step"))
+def _adamw_table(tensors, table, num_segments, num_chunks, lr, wd, lr_mult, b1, b2, eps, found_inf, step,
+                 check_finite):
+    _K.adamw_table_step(table, num_segments, num_chunks, list(lr), list(wd), lr_mult, b1, b2, eps, found_inf, step,
+                        check_finite)
+
+
+_adamw_table.register_fake(_none)
+
+
+def adamw_table_step(tensors, table, num_segments, num_chunks, lr, wd, lr_mult, b1, b2, eps, found_inf, step,
+                     check_finite=True):
+    torch.ops.ssl_mae.adamw_table(list(tensors), table, int(num_segments), int(num_chunks), [float(x) for x in lr],
+                                  [float(x) for x in wd], float(lr_mult), float(b1), float(b2), float(eps),
+                                  found_inf, step, bool(check_finite))
+
+
 # ============================================================================ FedAvg / clip pipeline
 @_op("fedavg_weighted_sum", "(Tensor[] bufs, float[] weights) -> Tensor")
 def _fedavg_weighted_sum(bufs, weights):
