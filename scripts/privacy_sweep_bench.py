@@ -60,8 +60,7 @@ def main():
     args = ap.parse_args()
     from ssl_mae_amd import run_privacy as RP
     from ssl_mae_amd.build import build
-    from ssl_mae_amd.finetune import VideoClassifier
-    from ssl_mae_amd.run_dynamic import load_finetune_ckpt
+    from ssl_mae_amd.finetune import VideoClassifier, load_finetune_ckpt
     from ssl_mae_amd.utils import load_config, set_seed
     if not torch.cuda.is_available():
         raise RuntimeError("privacy_sweep_bench needs an MI355X")

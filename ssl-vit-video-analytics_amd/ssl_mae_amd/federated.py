@@ -27,12 +27,14 @@ cheaper but its ring order breaks bit-exactness, and the exchange happens once
 per round).  Counters take a MAX all-reduce; other integer buffers come from
 rank 0 (the "first client").
 """
+import functools
 import random
 
 import torch
 import torch.distributed as dist
 
 from . import ops as K    # every kernel launch through the torch.ops.ssl_mae dispatcher
+from .utils import log_line
 
 
 def _is_float_tensor(t):
@@ -316,15 +318,6 @@ def estimate_comm_mb_per_round(global_state, num_clients_participating):
 
 
 # ------------------------------------------------------------------ host loop (fed_loop.py:65-150)
-def _logger(log_f):
-    def log(msg):
-        print(msg)
-        if log_f:
-            log_f.write(msg + "\n")
-            log_f.flush()
-    return log
-
-
 def _round_record(log, r, selected, losses, global_state, top1, top5):
     """fed_loop.py:125-147: the round's record and its log line."""
     comm_total_mb, model_mb = estimate_comm_mb_per_round(global_state, num_clients_participating=len(selected))
@@ -344,7 +337,7 @@ def run_fedavg(global_model, client_models, client_loaders, client_sizes, evalua
     num_clients = len(client_models)
     rng = random.Random(42)
     records = []
-    log = _logger(log_f)
+    log = functools.partial(log_line, log_f)
 
     for r in range(1, int(rounds) + 1):
         m = max(1, int(num_clients * float(client_fraction)))
@@ -373,7 +366,7 @@ def run_fedavg_fused(global_model, client_models, client_loaders, client_sizes, 
     rng = random.Random(42)
     records = []
     cohort = FedCohort(global_model, client_models)
-    log = _logger(log_f)
+    log = functools.partial(log_line, log_f)
 
     for r in range(1, int(rounds) + 1):
         m = max(1, int(num_clients * float(client_fraction)))

@@ -73,6 +73,24 @@ class HeadLinearFn(torch.autograd.Function):
         return dx, dw, db
 
 
+class TopCEFn(torch.autograd.Function):
+    """F.cross_entropy(logits, labels) through sm_logits_metrics; its dlogits output is the
+    gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, labels):
+        logits = logits.float().contiguous()
+        n = logits.shape[0]
+        dl = torch.empty_like(logits)
+        m = K.logits_metrics(logits, labels, 1, 1, dl, 1.0 / n)
+        ctx.save_for_backward(dl)
+        return (m[0, 0] / n).float()
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.saved_tensors[0] * g, None
+
+
 class TinyViTBackbone(TinyViT):
     """TinyViT (tiny_vit_21m_variant) with the backbone contract of
     MobileViTBackbone.forward (mobilevit.py:157-166): x [N,3,H,W] -> (feat [N,576,h,w],
@@ -160,6 +178,27 @@ def load_pretrained_ssl(model, ckpt_path):
     if unexpected:
         print(f"[INFO] Unexpected keys: {len(unexpected)}")
     return True
+
+
+def load_finetune_ckpt(model, ckpt_path):
+    """A fine-tuned classifier state (optionally under "model", run_dynamic.py:45-62), or an
+    SSL / encoder-only file through load_pretrained_ssl.  None: the portable-rule
+    initialisation, so the drivers run out of the box."""
+    if ckpt_path is None:
+        from .init_rule import apply_rule
+        apply_rule(model)
+        print("[INFO] No finetune checkpoint: portable-rule initialisation")
+        return
+    if not os.path.isfile(ckpt_path):
+        raise RuntimeError(f"[ERROR] finetune_ckpt not found: {ckpt_path}")
+    state = torch.load(ckpt_path, map_location="cpu", weights_only=True)
+    if isinstance(state, dict) and "model" in state and isinstance(state["model"], dict):
+        state = state["model"]
+    if any(k.startswith("classifier.") for k in state):
+        missing, unexpected = model.load_state_dict(state, strict=False)
+        print(f"[INFO] Loaded finetune checkpoint: {ckpt_path} (missing {len(missing)}, unexpected {len(unexpected)})")
+    else:
+        load_pretrained_ssl(model, ckpt_path)
 
 
 def set_requires_grad(module, flag):

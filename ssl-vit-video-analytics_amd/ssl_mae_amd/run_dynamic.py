@@ -12,14 +12,15 @@ sample is never encoded again.  Without `dataset.split` the driver runs on synth
 (random labels: the accuracy columns then only show chance), as bench.py does.
 """
 import argparse
-import os
 from pathlib import Path
 
 import torch
 
+from .driver import SyntheticBatches, build_classifier, merge_config, split_file_loader, start
 from .dynamic_infer import select_topk_frames, streaming_early_exit
-from .finetune import VideoClassifier, accuracy_topk, load_pretrained_ssl
-from .utils import load_config, set_seed
+from .finetune import accuracy_topk
+from .finetune import load_finetune_ckpt  # noqa: F401  (callers import it from here)
+from .utils import load_config, log_line
 
 MODES = ("early_exit", "frame_gating", "hybrid")
 EARLY_EXIT_HEADER = "threshold,top1,top5,avg_frames,avg_conf,avg_latency_ms,throughput_fps\n"
@@ -39,14 +40,7 @@ DEFAULTS = {
 def resolve_config(cfg, mode=None, ckpt=None, save_dir=None):
     """The file's values over DEFAULTS, the command line over both; validates the mode, the
     gating score and the list-valued keys."""
-    out = {sec: dict(vals) for sec, vals in DEFAULTS.items()}
-    for sec, vals in (cfg or {}).items():
-        if sec not in out:
-            raise ValueError(f"[ERROR] Unknown config section: {sec}")
-        unknown = set(vals or {}) - set(out[sec])
-        if unknown:
-            raise ValueError(f"[ERROR] Unknown keys in {sec}: {sorted(unknown)}")
-        out[sec].update(vals or {})
+    out = merge_config(DEFAULTS, cfg)
     if mode is not None:
         out["dynamic"]["mode"] = mode
     if ckpt is not None:
@@ -65,83 +59,23 @@ def resolve_config(cfg, mode=None, ckpt=None, save_dir=None):
     return out
 
 
-class SyntheticLoader:
-    """num_batches fixed batches of uniform-noise clips whose frames differ in gain, with
-    random labels, already on the device."""
+class SyntheticLoader(SyntheticBatches):
+    """num_warmup + num_measure fixed batches of synthetic clips with random labels, already on
+    the device, seeded with `runtime.seed`."""
 
     def __init__(self, cfg, device):
         ds, rt = cfg["dataset"], cfg["runtime"]
-        self.batch_size = int(rt["batch_size"])
-        n = int(rt["num_warmup"]) + int(rt["num_measure"])
-        g = torch.Generator().manual_seed(int(rt["seed"]))
-        B, T, S = self.batch_size, int(ds["clip_len"]), int(ds["image_size"])
-        self.batches = []
-        for _ in range(max(n, 1)):
-            clip = (torch.rand(B, 3, T, S, S, generator=g) - 0.45) / 0.226 * (0.3 + 1.4 * torch.rand(B, 1, T, 1, 1, generator=g))
-            self.batches.append((clip.to(device), torch.randint(0, int(ds["num_classes"]), (B,), generator=g).to(device)))
-
-    def __iter__(self):
-        return iter(self.batches)
+        super().__init__(int(rt["num_warmup"]) + int(rt["num_measure"]), rt["batch_size"], ds["clip_len"],
+                         ds["image_size"], device, seed=rt["seed"], num_classes=ds["num_classes"])
 
 
 def split_loader(cfg, device, shuffle=False, drop_last=False, seed=None):
-    """`dataset.split`: lines of `<frame directory> <label>`; frames decoded on the host at
-    their own size, resized to `image_size` and normalised on the device
-    (mae_loader.ClipResizer).  `shuffle` / `drop_last` (training loaders) draw their order
-    from a generator seeded with `seed`."""
-    from .mae_loader import ClipResizer, LazyVideoMAEDataset, collate_raw
+    """`dataset.split` (lines of `<frame directory> <label>`) through driver.split_file_loader;
+    `shuffle` / `drop_last` draw their order from a generator seeded with `seed`."""
     ds, rt = cfg["dataset"], cfg["runtime"]
-    data = LazyVideoMAEDataset(ds["split"], clip_len=int(ds["clip_len"]), stride=int(ds["stride"]),
-                               image_size=int(ds["image_size"]))
-    with open(ds["split"]) as f:
-        labels = [int(line.split()[1]) for line in f if line.strip()]
-    norm = ClipResizer(int(ds["image_size"]), device=device)
-
-    class Labelled(torch.utils.data.Dataset):
-        def __len__(self):
-            return len(data)
-
-        def __getitem__(self, i):
-            frames, valid = data[i]
-            return frames, valid, labels[i]
-
-    def collate(batch):
-        return collate_raw([b[:2] for b in batch]) + (torch.tensor([b[2] for b in batch]),)
-
-    gen = torch.Generator().manual_seed(int(seed)) if seed is not None else None
-    loader = torch.utils.data.DataLoader(Labelled(), batch_size=int(rt["batch_size"]), shuffle=bool(shuffle),
-                                         drop_last=bool(drop_last), generator=gen,
-                                         num_workers=int(rt["num_workers"]), collate_fn=collate)
-
-    class Normalised:
-        batch_size = loader.batch_size
-
-        def __iter__(self):
-            for packed, desc, label in loader:
-                yield norm(packed, desc, int(ds["clip_len"])), label.to(device)
-
-    return Normalised()
-
-
-def load_finetune_ckpt(model, ckpt_path):
-    """A fine-tuned classifier state (optionally under "model", run_dynamic.py:45-62), or an
-    SSL / encoder-only file through finetune.load_pretrained_ssl.  None: the portable-rule
-    initialisation, so the driver runs out of the box."""
-    if ckpt_path is None:
-        from .init_rule import apply_rule
-        apply_rule(model)
-        print("[INFO] No finetune checkpoint: portable-rule initialisation")
-        return
-    if not os.path.isfile(ckpt_path):
-        raise RuntimeError(f"[ERROR] finetune_ckpt not found: {ckpt_path}")
-    state = torch.load(ckpt_path, map_location="cpu", weights_only=True)
-    if isinstance(state, dict) and "model" in state and isinstance(state["model"], dict):
-        state = state["model"]
-    if any(k.startswith("classifier.") for k in state):
-        missing, unexpected = model.load_state_dict(state, strict=False)
-        print(f"[INFO] Loaded finetune checkpoint: {ckpt_path} (missing {len(missing)}, unexpected {len(unexpected)})")
-    else:
-        load_pretrained_ssl(model, ckpt_path)
+    return split_file_loader(ds["split"], clip_len=ds["clip_len"], stride=ds["stride"], image_size=ds["image_size"],
+                             batch_size=rt["batch_size"], num_workers=rt["num_workers"], device=device,
+                             shuffle=shuffle, drop_last=drop_last, seed=seed)
 
 
 class _Timer:
@@ -175,9 +109,7 @@ def _autocast(cfg):
 
 def _emit(cfg, name, lines, log_f, msg=None):
     if msg:
-        print(msg)
-        log_f.write(msg + "\n")
-        log_f.flush()
+        log_line(log_f, msg)
     if lines is not None and cfg["output"]["save_csv"]:
         path = Path(cfg["output"]["save_dir"]) / name
         path.parent.mkdir(parents=True, exist_ok=True)
@@ -292,16 +224,8 @@ def main(argv=None):
     ap.add_argument("--save_dir", default=None, help="override output.save_dir")
     args = ap.parse_args(argv)
     cfg = resolve_config(load_config(args.config), args.mode, args.ckpt, args.save_dir)
-    set_seed(cfg["runtime"]["seed"])
-    if not torch.cuda.is_available():
-        raise RuntimeError("[ERROR] run_dynamic needs an MI355X: the HIP kernels have no CPU fallback")
-    device = torch.device("cuda")
-    from .build import build
-    build()
-    model = VideoClassifier(int(cfg["dataset"]["num_classes"]), embed_dim=int(cfg["model"]["embed_dim"]),
-                            img_size=int(cfg["dataset"]["image_size"]))
-    load_finetune_ckpt(model, cfg["model"]["finetune_ckpt"])
-    model.to(device).eval()
+    device = start("run_dynamic", cfg["runtime"]["seed"])
+    model = build_classifier(cfg, cfg["model"]["finetune_ckpt"], device).eval()
     loader = split_loader(cfg, device) if cfg["dataset"]["split"] else SyntheticLoader(cfg, device)
     save_dir = Path(cfg["output"]["save_dir"])
     save_dir.mkdir(parents=True, exist_ok=True)

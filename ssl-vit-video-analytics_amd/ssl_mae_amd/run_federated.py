@@ -14,24 +14,23 @@ state_dict path, with bit-identical model states.
 
 `make_class_shard_splits` / `read_split` / `write_split` are src/datasets/federated_split.py
 (same random.Random(seed) call order: the same seed writes the same files), `client_update` is
-src/federated/client_sim.py under bf16 autocast with the cross-entropy from sm_logits_metrics,
-`evaluate_topk` is run_federated.py:20-39 through the same kernel.  Without `dataset.train_split`
-the driver runs on labelled synthetic clips, partitioned by the same class-shard rule.
+src/federated/client_sim.py under bf16 autocast with the cross-entropy from sm_logits_metrics
+(driver.train_pass), `evaluate_topk` is run_federated.py:20-39 through the same kernel
+(driver.evaluate).  Without `dataset.train_split` the driver runs on labelled synthetic clips
+(driver.SyntheticClips), partitioned by the same class-shard rule.
 """
 import argparse
-import csv
+import functools
 import random
 from collections import defaultdict
 from pathlib import Path
 
 import torch
 
-from . import ops as K    # every kernel launch through the torch.ops.ssl_mae dispatcher
+from .driver import SyntheticClips, build_classifier, evaluate, merge_config, split_file_loader, start, train_pass
 from .federated import bytes_to_mb, run_fedavg, run_fedavg_fused
-from .finetune import VideoClassifier
-from .run_dynamic import load_finetune_ckpt, split_loader
-from .temporal_ssl import TopCEFn
-from .utils import load_config, set_seed
+from .utils import load_config, log_line
+from .utils import write_csv as _write_csv
 
 CLIENT_STATS_HEADER = "client,num_samples,num_classes,classes\n"
 FED_COLUMNS = ("round", "val_top1", "val_top5", "avg_local_loss", "clients", "model_mb", "comm_mb_round",
@@ -60,22 +59,7 @@ DEFAULTS = {
 def resolve_config(cfg, save_dir=None, exchange=None):
     """The file's values over DEFAULTS, the command line over both; unknown sections or keys
     raise, and so does `non_iid.enabled: false` (run_federated.py:263-264)."""
-    out = {sec: dict(vals) for sec, vals in DEFAULTS.items()}
-    out["federated"]["non_iid"] = dict(DEFAULTS["federated"]["non_iid"])
-    for sec, vals in (cfg or {}).items():
-        if sec not in out:
-            raise ValueError(f"[ERROR] Unknown config section: {sec}")
-        vals = dict(vals or {})
-        unknown = set(vals) - set(out[sec])
-        if unknown:
-            raise ValueError(f"[ERROR] Unknown keys in {sec}: {sorted(unknown)}")
-        if sec == "federated" and "non_iid" in vals:
-            non_iid = dict(vals.pop("non_iid") or {})
-            unknown = set(non_iid) - set(out[sec]["non_iid"])
-            if unknown:
-                raise ValueError(f"[ERROR] Unknown keys in federated.non_iid: {sorted(unknown)}")
-            out[sec]["non_iid"].update(non_iid)
-        out[sec].update(vals)
+    out = merge_config(DEFAULTS, cfg)
     if save_dir is not None:
         out["output"]["save_dir"] = save_dir
     if exchange is not None:
@@ -159,118 +143,24 @@ def make_class_shard_splits(base_split_file, num_clients, shards_per_client=6, s
     return out_paths, out_stats
 
 
-# ------------------------------------------------------------------ loaders
-class SyntheticClips:
-    """`n` labelled uniform-noise clips on the device (run_dynamic.SyntheticLoader's pixels), named
-    `synthetic/<index>` in split files so the class-shard rule partitions them like real ones."""
-
-    def __init__(self, cfg, n, seed, device):
-        ds = cfg["dataset"]
-        g = torch.Generator().manual_seed(int(seed))
-        T, S = int(ds["clip_len"]), int(ds["image_size"])
-        clips = (torch.rand(n, 3, T, S, S, generator=g) - 0.45) / 0.226 * (0.3 + 1.4 * torch.rand(n, 1, T, 1, 1, generator=g))
-        self.clips = clips.to(device)
-        self.labels = torch.randint(0, int(ds["num_classes"]), (n,), generator=g)
-
-    def items(self):
-        return [(f"synthetic/{i}", int(y)) for i, y in enumerate(self.labels.tolist())]
-
-    def loader(self, items, batch_size, shuffle, seed):
-        idx = torch.tensor([int(p.split("/")[1]) for p, _ in items], dtype=torch.long)
-        return _SyntheticLoader(self, idx, int(batch_size), bool(shuffle), int(seed))
-
-
-class _SyntheticLoader:
-    """Batches of a SyntheticClips subset; shuffle implies drop_last (utils_fed.build_loader)
-    and a fresh permutation per pass from one seeded generator."""
-
-    def __init__(self, data, idx, batch_size, shuffle, seed):
-        self.data, self.idx, self.batch_size, self.shuffle = data, idx, batch_size, shuffle
-        self.gen = torch.Generator().manual_seed(seed)
-
-    def __len__(self):
-        n = len(self.idx)
-        return n // self.batch_size if self.shuffle else (n + self.batch_size - 1) // self.batch_size
-
-    def __iter__(self):
-        idx = self.idx[torch.randperm(len(self.idx), generator=self.gen)] if self.shuffle else self.idx
-        labels = self.data.labels.to(self.data.clips.device)
-        for b in range(len(self)):
-            sel = idx[b * self.batch_size:(b + 1) * self.batch_size].to(self.data.clips.device)
-            yield self.data.clips[sel], labels[sel]
-
-
-def _split_file_loader(cfg, split_file, batch_size, shuffle, seed, device):
-    shim = {"dataset": dict(cfg["dataset"], split=str(split_file)),
-            "runtime": {"batch_size": int(batch_size), "num_workers": cfg["runtime"]["num_workers"]}}
-    return split_loader(shim, device, shuffle=shuffle, drop_last=shuffle, seed=seed)
-
-
 # ------------------------------------------------------------------ client update / evaluation
-def _train_pass(model, loader, opt, device, amp, loss_sum):
-    """One pass over `loader` (client_sim.py:45-65); adds loss * batch to the device scalar
-    `loss_sum` and returns the number of samples."""
-    total = 0
-    for clip, y in loader:
-        clip = clip.to(device, non_blocking=True)
-        y = y.to(device, non_blocking=True).long()
-        opt.zero_grad(set_to_none=True)
-        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bool(amp)):
-            logits = model(clip)
-        loss = TopCEFn.apply(logits, y)
-        loss.backward()
-        opt.step()
-        bs = int(y.size(0))
-        loss_sum += loss.detach().double() * bs
-        total += bs
-    return total
-
-
 def client_update(model, loader, device, epochs=1, lr=3e-4, weight_decay=0.01, amp=True):
     """client_sim.py:30-67: `epochs` local passes with a fresh AdamW over all parameters; returns
     the average loss.  The running loss * batch sum stays on the device: one read-back per call."""
     model.train()
     opt = torch.optim.AdamW(model.parameters(), lr=float(lr), weight_decay=float(weight_decay))
-    loss_sum = torch.zeros((), dtype=torch.float64, device=device)
+    sums = torch.zeros(2, dtype=torch.float64, device=device)     # (loss, loss * batch)
     total = 0
     for _ in range(int(epochs)):
-        total += _train_pass(model, loader, opt, device, amp, loss_sum)
-    return float(loss_sum.item()) / max(1, total)
+        _, samples = train_pass(model, loader, opt, device, amp, sums)
+        total += samples
+    return float(sums[1].item()) / max(1, total)
 
 
-@torch.no_grad()
 def evaluate_topk(model, loader, device):
-    """run_federated.py:20-39 -> (top1, top5) with k = min(5, classes), counted by
-    sm_logits_metrics (its tie rule: kernels.logits_metrics) and read back once."""
-    model.eval()
-    hits = torch.zeros(2, dtype=torch.float64, device=device)
-    total = 0
-    for clip, y in loader:
-        clip = clip.to(device, non_blocking=True)
-        y = y.to(device, non_blocking=True).long()
-        logits = model(clip).float().contiguous()
-        hits += K.logits_metrics(logits, y, min(5, logits.shape[1]))[0, 2:4]
-        total += int(y.size(0))
-    top1, top5 = hits.cpu().tolist()
-    return top1 / max(1, total), top5 / max(1, total)
-
-
-def _write_csv(path, header, rows):
-    """utils.write_csv of the reference."""
-    path = Path(path)
-    path.parent.mkdir(parents=True, exist_ok=True)
-    with open(path, "w", encoding="utf-8", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=list(header))
-        w.writeheader()
-        for r in rows:
-            w.writerow(r)
-
-
-def _new_model(cfg, device):
-    model = VideoClassifier(int(cfg["dataset"]["num_classes"]), embed_dim=int(cfg["model"]["embed_dim"]),
-                            img_size=int(cfg["dataset"]["image_size"]))
-    load_finetune_ckpt(model, cfg["model"]["init_ckpt"])
-    return model.to(device)
+    """run_federated.py:20-39 -> (top1, top5) with k = min(5, classes): driver.evaluate."""
+    acc = evaluate(model, loader, device, topk=(1, 5))
+    return acc[1], acc[5]
 
 
 def train_centralized(cfg, device, train_loader, val_loader, out_dir, log=print):
@@ -288,15 +178,15 @@ def train_centralized(cfg, device, train_loader, val_loader, out_dir, log=print)
         return fed[key] if c_cfg[key] is None else c_cfg[key]
 
     loader = train_loader(int(pick("batch_size")))
-    model = _new_model(cfg, device)
+    model = build_classifier(cfg, cfg["model"]["init_ckpt"], device)
     model.train()
     opt = torch.optim.AdamW(model.parameters(), lr=float(pick("lr")), weight_decay=float(pick("weight_decay")))
     rows = []
     for ep in range(1, epochs + 1):
         model.train()
-        loss_sum = torch.zeros((), dtype=torch.float64, device=device)
-        total = _train_pass(model, loader, opt, device, cfg["runtime"]["amp"], loss_sum)
-        avg_loss = float(loss_sum.item()) / max(1, total)
+        sums = torch.zeros(2, dtype=torch.float64, device=device)
+        _, total = train_pass(model, loader, opt, device, cfg["runtime"]["amp"], sums)
+        avg_loss = float(sums[1].item()) / max(1, total)
         top1, top5 = evaluate_topk(model, val_loader, device)
         log(f"[INFO][Centralized] ep={ep}/{epochs} train_loss={avg_loss:.4f} val_top1={top1:.4f} "
             f"val_top5={top5:.4f}")
@@ -352,12 +242,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     cfg = resolve_config(load_config(args.config), args.save_dir, args.exchange)
     seed = int(cfg["runtime"]["seed"])
-    set_seed(seed)
-    if not torch.cuda.is_available():
-        raise RuntimeError("[ERROR] run_federated needs an MI355X: the HIP kernels have no CPU fallback")
-    device = torch.device("cuda")
-    from .build import build
-    build()
+    device = start("run_federated", seed)
     fed, ds = cfg["federated"], cfg["dataset"]
     out_dir = Path(cfg["output"]["save_dir"])
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -369,7 +254,10 @@ def main(argv=None):
         train_split, split_dir = Path(ds["train_split"]), Path(ds["train_split"]).parent
 
         def loader_of(split_file, bs, shuffle, s):
-            return _split_file_loader(cfg, split_file, bs, shuffle, s, device)
+            return split_file_loader(str(split_file), clip_len=ds["clip_len"], stride=ds["stride"],
+                                     image_size=ds["image_size"], batch_size=bs,
+                                     num_workers=cfg["runtime"]["num_workers"], device=device, shuffle=shuffle,
+                                     drop_last=shuffle, seed=s)
     else:
         # labelled synthetic clips, listed in a split file so the same class-shard rule applies
         split_dir = out_dir / "splits"
@@ -385,11 +273,7 @@ def main(argv=None):
     val_split = Path(ds["val_split"]) if ds["train_split"] else split_dir / "synthetic_val.txt"
 
     with open(out_dir / "federated.log", "a", encoding="utf-8") as log_f:
-        def log(msg):
-            print(msg)
-            log_f.write(msg + "\n")
-            log_f.flush()
-
+        log = functools.partial(log_line, log_f)
         log(f"[INFO] Federated experiment started, exchange={fed['exchange']}")
         val_loader = loader_of(val_split, batch_size, False, seed + 999)
         centralized_rows = train_centralized(cfg, device, lambda bs: loader_of(train_split, bs, True, seed + 123),
@@ -406,9 +290,8 @@ def main(argv=None):
             encoding="utf-8")
         log(f"[INFO] Saved client stats: {stats_csv}")
 
-        global_model = _new_model(cfg, device)
-        client_models = [VideoClassifier(int(ds["num_classes"]), embed_dim=int(cfg["model"]["embed_dim"]),
-                                         img_size=int(ds["image_size"])).to(device) for _ in range(num_clients)]
+        global_model = build_classifier(cfg, cfg["model"]["init_ckpt"], device)
+        client_models = [build_classifier(cfg, None, device, load=None) for _ in range(num_clients)]
         client_sizes, client_loaders = [], []
         for cid in range(num_clients):
             loader = loader_of(split_paths[cid], batch_size, True, seed + cid)

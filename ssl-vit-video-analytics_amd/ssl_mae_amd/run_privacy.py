@@ -25,9 +25,8 @@ from pathlib import Path
 import torch
 
 from . import privacy as P
-from .finetune import VideoClassifier
-from .run_dynamic import SyntheticLoader, load_finetune_ckpt, split_loader
-from .utils import load_config, set_seed
+from .driver import SyntheticBatches, build_classifier, merge_config, split_file_loader, start
+from .utils import load_config, log_line
 
 CSV_COLUMNS = ("sigma", "mask_ratio", "top1", "top5", "entropy", "attacker_top1", "per_vs_clean")
 CSV_HEADER = ",".join(CSV_COLUMNS) + "\n"
@@ -50,14 +49,7 @@ DEFAULTS = {
 def resolve_config(cfg, ckpt=None, save_dir=None):
     """The file's values over DEFAULTS, the command line over both; unknown sections or keys
     raise, the two grid lists are coerced to float and must not be empty."""
-    out = {sec: dict(vals) for sec, vals in DEFAULTS.items()}
-    for sec, vals in (cfg or {}).items():
-        if sec not in out:
-            raise ValueError(f"[ERROR] Unknown config section: {sec}")
-        unknown = set(vals or {}) - set(out[sec])
-        if unknown:
-            raise ValueError(f"[ERROR] Unknown keys in {sec}: {sorted(unknown)}")
-        out[sec].update(vals or {})
+    out = merge_config(DEFAULTS, cfg)
     if ckpt is not None:
         out["model"]["finetune_ckpt"] = ckpt
     if save_dir is not None:
@@ -83,26 +75,20 @@ def format_row(row):
     return ",".join(str(v) for v in vals) + "\n"
 
 
-def _log(log_f, msg):
-    print(msg)
-    log_f.write(msg + "\n")
-    log_f.flush()
-
-
 def run_visual_privacy(cfg, log_f):
     if cfg["visual_privacy"]["enabled"]:
-        _log(log_f, "[INFO] visual_privacy needs OpenCV (YuNet face detection + GaussianBlur) and is not part of "
-                    "this build -> skip")
+        log_line(log_f, "[INFO] visual_privacy needs OpenCV (YuNet face detection + GaussianBlur) and is not part of "
+                        "this build -> skip")
 
 
 def _loader(cfg, device):
-    if cfg["dataset"]["split"]:
-        shim = {"dataset": cfg["dataset"], "runtime": cfg["runtime"]}
-        return split_loader(shim, device)
-    rt = cfg["runtime"]
-    shim = {"dataset": cfg["dataset"], "runtime": {"batch_size": rt["batch_size"], "num_warmup": 0,
-                                                   "num_measure": rt["num_batches"], "seed": rt["seed"]}}
-    return SyntheticLoader(shim, device)
+    ds, rt = cfg["dataset"], cfg["runtime"]
+    if ds["split"]:
+        return split_file_loader(ds["split"], clip_len=ds["clip_len"], stride=ds["stride"],
+                                 image_size=ds["image_size"], batch_size=rt["batch_size"],
+                                 num_workers=rt["num_workers"], device=device)
+    return SyntheticBatches(rt["num_batches"], rt["batch_size"], ds["clip_len"], ds["image_size"], device,
+                            seed=rt["seed"], num_classes=ds["num_classes"])
 
 
 @torch.no_grad()
@@ -124,7 +110,7 @@ def run_feature_privacy(model, loader, device, cfg, log_f):
     save_dir = Path(cfg["output"]["save_dir"])
     out_csv = save_dir / "feature_privacy.csv"
     if not fp["enabled"]:
-        _log(log_f, "[INFO] feature_privacy disabled -> skip")
+        log_line(log_f, "[INFO] feature_privacy disabled -> skip")
         return {"rows": [], "csv": out_csv}
     nc = int(cfg["dataset"]["num_classes"])
     k5 = min(5, nc)
@@ -134,7 +120,7 @@ def run_feature_privacy(model, loader, device, cfg, log_f):
     _, ent, top1, _ = P.logits_metrics(logits_clean, y, k5)
     clean_top1, clean_ent = top1.item(), ent.item()
     t1 = time.perf_counter()
-    _log(log_f, f"[INFO] Clean embeddings -> Top-1={clean_top1:.4f}, Entropy={clean_ent:.4f}")
+    log_line(log_f, f"[INFO] Clean embeddings -> Top-1={clean_top1:.4f}, Entropy={clean_ent:.4f}")
 
     P.route_head(model)                          # model.classifier on the project's GEMM
     cfgs = P.grid_configs(fp["noise_sigmas"], fp["mask_ratios"], int(cfg["runtime"]["seed"]))
@@ -156,11 +142,12 @@ def run_feature_privacy(model, loader, device, cfg, log_f):
                "per_vs_clean": P.privacy_exposure_rate(clean_top1, a_)}
         rows.append(row)
         lines.append(format_row(row))
-        _log(log_f, f"[INFO] sigma={sigma} mask={ratio} | top1={t1_:.4f} top5={t5_:.4f} | attacker={a_:.4f} | "
-                    f"ent={e_:.4f}")
+        log_line(log_f, f"[INFO] sigma={sigma} mask={ratio} | top1={t1_:.4f} top5={t5_:.4f} | attacker={a_:.4f} | "
+                        f"ent={e_:.4f}")
     out_csv.write_text("".join(lines), encoding="utf-8")
-    _log(log_f, f"[INFO] Saved feature privacy CSV: {out_csv}")
-    _log(log_f, f"[INFO] embedding pass {t1 - t0:.3f} s ({N} clips), sweep {t2 - t1:.3f} s ({G} configurations)")
+    log_line(log_f, f"[INFO] Saved feature privacy CSV: {out_csv}")
+    log_line(log_f,
+             f"[INFO] embedding pass {t1 - t0:.3f} s ({N} clips), sweep {t2 - t1:.3f} s ({G} configurations)")
     return {"rows": rows, "clean_top1": clean_top1, "clean_entropy": clean_ent, "embed_s": t1 - t0,
             "sweep_s": t2 - t1, "csv": out_csv}
 
@@ -172,25 +159,17 @@ def main(argv=None):
     ap.add_argument("--save_dir", default=None, help="override output.save_dir")
     args = ap.parse_args(argv)
     cfg = resolve_config(load_config(args.config), args.ckpt, args.save_dir)
-    set_seed(cfg["runtime"]["seed"])
-    if not torch.cuda.is_available():
-        raise RuntimeError("[ERROR] run_privacy needs an MI355X: the HIP kernels have no CPU fallback")
-    device = torch.device("cuda")
-    from .build import build
-    build()
+    device = start("run_privacy", cfg["runtime"]["seed"])
     save_dir = Path(cfg["output"]["save_dir"])
     save_dir.mkdir(parents=True, exist_ok=True)
     with open(save_dir / "privacy.log", "a", encoding="utf-8") as log_f:
-        _log(log_f, "[INFO] Privacy evaluation started")
+        log_line(log_f, "[INFO] Privacy evaluation started")
         run_visual_privacy(cfg, log_f)
         result = {"rows": []}
         if cfg["feature_privacy"]["enabled"]:
-            model = VideoClassifier(int(cfg["dataset"]["num_classes"]), embed_dim=int(cfg["model"]["embed_dim"]),
-                                    img_size=int(cfg["dataset"]["image_size"]))
-            load_finetune_ckpt(model, cfg["model"]["finetune_ckpt"])
-            model.to(device).eval()
+            model = build_classifier(cfg, cfg["model"]["finetune_ckpt"], device).eval()
             result = run_feature_privacy(model, _loader(cfg, device), device, cfg, log_f)
-        _log(log_f, "[INFO] Privacy evaluation finished.")
+        log_line(log_f, "[INFO] Privacy evaluation finished.")
     return result
 
 

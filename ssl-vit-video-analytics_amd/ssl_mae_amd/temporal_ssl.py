@@ -40,11 +40,13 @@ import torch
 import torch.nn as nn
 
 from . import ops as K    # every kernel launch through the torch.ops.ssl_mae dispatcher
-from .finetune import SegMeanFn, tiny_vit_backbone
+from .driver import SyntheticBatches as SyntheticClips    # drawn per batch: pixels, gain; no labels
+from .driver import split_file_loader, start
+from .finetune import SegMeanFn, TopCEFn, tiny_vit_backbone
 from .functions import BlockFn, G, Mode, W, _bn_params, _done, _touch, _train_bn_only
 from .mae_vit_adapter import _St, ensure_flat, make_flat, next_seed_base
 from .optim import FusedAdamW, GradScaler
-from .utils import load_config, set_seed
+from .utils import load_config
 
 
 # ============================================================ autograd Functions
@@ -65,24 +67,6 @@ class MFMLossFn(torch.autograd.Function):
         pred, teacher, idx, stats = ctx.saved_tensors
         dpred = K.mfm_loss_bwd(pred, teacher, idx, stats, g.float()[2:3].contiguous(), ctx.w[0], ctx.w[1])
         return dpred, None, None, None, None, None, None
-
-
-class TopCEFn(torch.autograd.Function):
-    """F.cross_entropy(logits, labels) through sm_logits_metrics; its dlogits output is the
-    gradient."""
-
-    @staticmethod
-    def forward(ctx, logits, labels):
-        logits = logits.float().contiguous()
-        n = logits.shape[0]
-        dl = torch.empty_like(logits)
-        m = K.logits_metrics(logits, labels, 1, 1, dl, 1.0 / n)
-        ctx.save_for_backward(dl)
-        return (m[0, 0] / n).float()
-
-    @staticmethod
-    def backward(ctx, g):
-        return ctx.saved_tensors[0] * g, None
 
 
 class FlatLinearFn(torch.autograd.Function):
@@ -460,49 +444,14 @@ def train_one_epoch(model, ema, loader, opt, scaler, sch, device, cfg, epoch):
 
 
 # ============================================================ Main
-class SyntheticClips:
-    """`steps` fixed batches of uniform-noise clips whose frames differ in gain, on the device
-    (no split configured), as run_dynamic.SyntheticLoader."""
-
-    def __init__(self, steps, batch_size, clip_len, image_size, device, seed=42):
-        g = torch.Generator().manual_seed(int(seed))
-        B, T, S = int(batch_size), int(clip_len), int(image_size)
-        self.batches = []
-        for _ in range(max(1, int(steps))):
-            clip = (torch.rand(B, 3, T, S, S, generator=g) - 0.45) / 0.226 \
-                * (0.3 + 1.4 * torch.rand(B, 1, T, 1, 1, generator=g))
-            self.batches.append(clip.to(device))
-
-    def __len__(self):
-        return len(self.batches)
-
-    def __iter__(self):
-        return iter(self.batches)
-
-
 def split_loader(cfg, device):
-    """Lines of `<frame directory> ...`: frames decoded on the host (LazyVideoMAEDataset with
-    transform=None) at their own size, resized to `image_size` and normalised on the device,
-    RGB order (ClipResizer(bgr_swap=False))."""
-    from .mae_loader import ClipResizer, LazyVideoMAEDataset, collate_raw
+    """Lines of `<frame directory> ...` under `split_root` through driver.split_file_loader:
+    unlabelled, shuffled, RGB order (ClipResizer(bgr_swap=False))."""
     ds, tr = cfg["dataset"], cfg["training"]
-    path = os.path.join(ds.get("split_root", ""), ds["train_split"])
-    data = LazyVideoMAEDataset(path, clip_len=int(ds["clip_len"]), stride=int(ds["stride"]),
-                               image_size=int(ds["image_size"]), transform=None)
-    loader = torch.utils.data.DataLoader(data, batch_size=int(tr["batch_size"]), shuffle=True,
-                                         num_workers=int(tr.get("num_workers", 4)), pin_memory=True, drop_last=True,
-                                         collate_fn=collate_raw)
-    norm = ClipResizer(int(ds["image_size"]), bgr_swap=False, device=device)
-
-    class Normalised:
-        def __len__(self):
-            return len(loader)
-
-        def __iter__(self):
-            for packed, desc in loader:
-                yield norm(packed, desc, int(ds["clip_len"]))
-
-    return Normalised()
+    return split_file_loader(os.path.join(ds.get("split_root", ""), ds["train_split"]), clip_len=ds["clip_len"],
+                             stride=ds["stride"], image_size=ds["image_size"], batch_size=tr["batch_size"],
+                             num_workers=tr.get("num_workers", 4), device=device, labelled=False, bgr_swap=False,
+                             shuffle=True, drop_last=True, pin_memory=True)
 
 
 DATASET_DEFAULTS = {"clip_len": 16, "stride": 2, "image_size": 112, "train_split": None, "split_root": "data/splits",
@@ -557,12 +506,7 @@ def main(argv=None):
             tr[key] = getattr(args, key)
     if args.synthetic_steps is not None:
         cfg["dataset"]["synthetic_steps"] = args.synthetic_steps
-    set_seed(cfg.get("seed", 42))
-    if not torch.cuda.is_available():
-        raise RuntimeError("[ERROR] train_ssl needs an MI355X: the HIP kernels have no CPU fallback")
-    device = torch.device("cuda")
-    from .build import build
-    build()
+    device = start("train_ssl", cfg.get("seed", 42))
     ds = cfg["dataset"]
     split = ds.get("train_split")
     if split and os.path.isfile(os.path.join(ds.get("split_root", ""), split)):

@@ -9,30 +9,28 @@ Flow (train_finetune.py:213-353): loaders -> model -> the mode's SSL load and fr
 (:280-313) -> optimizer -> per epoch: the two_stage unfreeze at epoch stage1_epochs + 1 (fresh
 optimizer state), one training pass, one validation pass, a checkpoint whenever validation top-1
 improves.  Outputs: `{log_dir}/finetune_{mode}.log`, `{save_dir}/{mode}/finetune_epoch_{E}_top1_
-{acc:.4f}.pth` (model.state_dict(), what run_dynamic.load_finetune_ckpt reads) and
+{acc:.4f}.pth` (model.state_dict(), what finetune.load_finetune_ckpt reads) and
 `{save_dir}/{mode}/finetune_summary.csv`.
 
 The step: bf16 autocast when `training.amp`, the cross-entropy through sm_logits_metrics
-(temporal_ssl.TopCEFn), optim.GroupedAdamW over finetune.param_groups (one sm_adamw_table launch
+(finetune.TopCEFn, driver.train_pass), optim.GroupedAdamW over finetune.param_groups (one sm_adamw_table launch
 for every parameter group; the non-finite skip happens inside it, so optim.GradScaler is the
 shim).  `optimizer.type: adamw_torch` keeps torch.optim.AdamW over the same groups.  The running
 loss stays on the device: one read-back per log_interval and one per epoch.  Without
-`dataset.train_split` the driver runs on labelled synthetic clips (run_federated.SyntheticClips).
+`dataset.train_split` the driver runs on labelled synthetic clips (driver.SyntheticClips).
 """
 import argparse
-import csv
+import functools
 import os
 import time
 from pathlib import Path
 
 import torch
 
-from . import ops as K    # every kernel launch through the torch.ops.ssl_mae dispatcher
-from .finetune import (VideoClassifier, epoch_lr_mult, load_pretrained_ssl, param_groups, resolve_mode,
-                       set_requires_grad)
+from . import driver
+from .finetune import epoch_lr_mult, load_pretrained_ssl, param_groups, resolve_mode, set_requires_grad
 from .optim import GradScaler, GroupedAdamW
-from .temporal_ssl import TopCEFn
-from .utils import load_config, set_seed
+from .utils import load_config, log_line, write_csv
 
 SUMMARY_COLUMNS = ("epoch", "train_loss", "val_top1", "val_topk", "lr", "seconds")
 OPTIMIZERS = {"adamw": "fused", "adamw_torch": "torch"}
@@ -59,14 +57,7 @@ def resolve_config(cfg, mode=None, pretrained_ssl=None, epochs=None, batch_size=
     """The file's values over DEFAULTS, the command line over both; unknown sections or keys
     raise, and so do an unknown mode, two_stage without stage1_epochs and an SSL mode whose
     checkpoint is missing (train_finetune.py:198-210, :284-286, :306-307)."""
-    out = {sec: dict(vals) for sec, vals in DEFAULTS.items()}
-    for sec, vals in (cfg or {}).items():
-        if sec not in out:
-            raise ValueError(f"[ERROR] Unknown config section: {sec}")
-        unknown = set(vals or {}) - set(out[sec])
-        if unknown:
-            raise ValueError(f"[ERROR] Unknown keys in {sec}: {sorted(unknown)}")
-        out[sec].update(vals or {})
+    out = driver.merge_config(DEFAULTS, cfg)
     tr = out["training"]
     out["experiment"]["mode"] = resolve_mode(out, mode)
     if pretrained_ssl is not None:
@@ -135,60 +126,30 @@ def set_lr_mult(optimizer, base_lrs, mult):
 
 
 def train_one_epoch(model, loader, optimizer, scaler, device, cfg, log, step_hook=None):
-    """train_finetune.py:84-124 with the loss sum kept on the device; returns the average loss."""
+    """train_finetune.py:84-124 as driver.train_pass, the loss sum kept on the device; returns the
+    average loss over the steps."""
     model.train()
     tr = cfg["training"]
-    loss_sum = torch.zeros((), dtype=torch.float64, device=device)
-    steps = 0
     t0 = time.time()
-    n = len(loader) if hasattr(loader, "__len__") else None
-    for step, (clip, label) in enumerate(loader):
-        clip = clip.to(device, non_blocking=True)
-        label = label.to(device, non_blocking=True).long()
-        optimizer.zero_grad(set_to_none=True)
-        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bool(tr["amp"])):
-            logits = model(clip)
-        loss = TopCEFn.apply(logits, label)
-        scaler.scale(loss).backward()
-        scaler.step(optimizer)
-        scaler.update()
-        loss_sum += loss.detach().double()
-        steps += 1
+    n = len(loader) if hasattr(loader, "__len__") else "?"
+
+    def on_step(step, loss, logits, label):
         if step_hook is not None:
-            step_hook(step, logits.detach(), label)
+            step_hook(step, logits, label)
         if (step + 1) % int(tr["log_interval"]) == 0:
-            log(f"[INFO] step={step + 1}/{n if n is not None else '?'} loss={loss.item():.4f}")
-    avg_loss = float(loss_sum.item()) / max(1, steps)
+            log(f"[INFO] step={step + 1}/{n} loss={loss.item():.4f}")
+
+    sums = torch.zeros(2, dtype=torch.float64, device=device)     # (loss, loss * batch)
+    steps, _ = driver.train_pass(model, loader, optimizer, device, tr["amp"], sums, scaler, on_step)
+    avg_loss = float(sums[0].item()) / max(1, steps)
     log(f"[INFO] Epoch train finished, avg_loss={avg_loss:.4f}, time={time.time() - t0:.1f}s")
     return avg_loss
 
 
-@torch.no_grad()
 def evaluate(model, loader, device, topk, log, split="val"):
-    """train_finetune.py:127-153 -> {k: accuracy} for k = 1 and every k of `topk`; hits counted on the device by
-    sm_logits_metrics (its tie rule: kernels.logits_metrics), each k capped at the class count,
-    read back once per pass."""
-    model.eval()
-    ks = [k for k in dict.fromkeys(topk) if k != 1]
-    hits = torch.zeros(1 + len(ks), dtype=torch.float64, device=device)
-    total = 0
-    for clip, label in loader:
-        clip = clip.to(device, non_blocking=True)
-        label = label.to(device, non_blocking=True).long()
-        logits = model(clip).float().contiguous()
-        nc = logits.shape[1]
-        if ks:
-            for i, k in enumerate(ks):
-                m = K.logits_metrics(logits, label, min(k, nc))
-                hits[1 + i] += m[0, 3]
-            hits[0] += m[0, 2]
-        else:
-            hits[0] += K.logits_metrics(logits, label, 1)[0, 2]
-        total += int(label.size(0))
-    counts = hits.cpu().tolist()
-    acc = {1: counts[0] / max(1, total)}
-    for i, k in enumerate(ks):
-        acc[k] = counts[1 + i] / max(1, total)
+    """train_finetune.py:127-153 -> {k: accuracy} for k = 1 and every k of `topk`
+    (driver.evaluate) and the pass's log line."""
+    acc = driver.evaluate(model, loader, device, topk)
     log(f"[INFO] {split} results: " + ", ".join(f"Top-{k}: {acc[k]:.4f}" for k in topk))
     return acc
 
@@ -206,17 +167,15 @@ def build_loaders(cfg, device):
     ds, tr, seed = cfg["dataset"], cfg["training"], int(cfg["runtime"]["seed"])
     bs = int(tr["batch_size"])
     if ds["train_split"]:
-        from .run_dynamic import split_loader
-
         def of(split, shuffle, s):
-            shim = {"dataset": dict(ds, split=str(split)),
-                    "runtime": {"batch_size": bs, "num_workers": cfg["runtime"]["num_workers"]}}
-            return split_loader(shim, device, shuffle=shuffle, drop_last=shuffle, seed=s)
+            return driver.split_file_loader(str(split), clip_len=ds["clip_len"], stride=ds["stride"],
+                                            image_size=ds["image_size"], batch_size=bs,
+                                            num_workers=cfg["runtime"]["num_workers"], device=device,
+                                            shuffle=shuffle, drop_last=shuffle, seed=s)
 
         return of(ds["train_split"], True, seed), of(ds["val_split"], False, seed + 999)
-    from .run_federated import SyntheticClips
-    train_set = SyntheticClips(cfg, int(cfg["synthetic"]["num_train"]), seed, device)
-    val_set = SyntheticClips(cfg, int(cfg["synthetic"]["num_val"]), seed + 999, device)
+    train_set = driver.SyntheticClips(cfg, int(cfg["synthetic"]["num_train"]), seed, device)
+    val_set = driver.SyntheticClips(cfg, int(cfg["synthetic"]["num_val"]), seed + 999, device)
     return train_set.loader(train_set.items(), bs, True, seed), val_set.loader(val_set.items(), bs, False, seed + 999)
 
 
@@ -236,12 +195,7 @@ def main(argv=None, hooks=None):
                          args.save_dir, args.optimizer)
     hooks = hooks or {}
     mode, tr = cfg["experiment"]["mode"], cfg["training"]
-    set_seed(int(cfg["runtime"]["seed"]))
-    if not torch.cuda.is_available():
-        raise RuntimeError("[ERROR] train_finetune needs an MI355X: the HIP kernels have no CPU fallback")
-    device = torch.device("cuda")
-    from .build import build
-    build()
+    device = driver.start("train_finetune", cfg["runtime"]["seed"])
     print(f"[INFO] Using device: {device}")
     print(f"[INFO] Finetune mode: {mode}")
 
@@ -251,13 +205,13 @@ def main(argv=None, hooks=None):
     save_dir.mkdir(parents=True, exist_ok=True)
     train_loader, val_loader = build_loaders(cfg, device)
 
-    model = VideoClassifier(int(cfg["dataset"]["num_classes"]), embed_dim=int(cfg["model"]["embed_dim"]),
-                            img_size=int(cfg["dataset"]["image_size"]))
-    if mode == "ft_random":
-        print("[INFO] ft_random: skip SSL loading (random init)")
-    elif not load_pretrained_ssl(model, cfg["model"]["pretrained_ssl"]):
-        raise RuntimeError("[ERROR] SSL mode selected but pretrained_ssl checkpoint not found!")
-    model = model.to(device)
+    def load_for_mode(model, ssl):
+        if mode == "ft_random":
+            print("[INFO] ft_random: skip SSL loading (random init)")
+        elif not load_pretrained_ssl(model, ssl):
+            raise RuntimeError("[ERROR] SSL mode selected but pretrained_ssl checkpoint not found!")
+
+    model = driver.build_classifier(cfg, cfg["model"]["pretrained_ssl"], device, load=load_for_mode)
     frozen, two_stage = freeze_rule(cfg)
     set_requires_grad(model.backbone, not frozen)
     if frozen:
@@ -273,11 +227,7 @@ def main(argv=None, hooks=None):
 
     rows, ckpts = [], []
     with open(log_dir / f"finetune_{mode}.log", "a", encoding="utf-8") as log_f:
-        def log(msg):
-            print(msg)
-            log_f.write(msg + "\n")
-            log_f.flush()
-
+        log = functools.partial(log_line, log_f)
         best_top1 = -1.0      # the first validated epoch always leaves a checkpoint
         for epoch in range(1, epochs + 1):
             if two_stage and epoch == stage1 + 1:
@@ -302,10 +252,7 @@ def main(argv=None, hooks=None):
             if "epoch" in hooks:
                 hooks["epoch"](epoch, model, optimizer)
         summary = save_dir / "finetune_summary.csv"
-        with open(summary, "w", encoding="utf-8", newline="") as f:
-            w = csv.DictWriter(f, fieldnames=list(SUMMARY_COLUMNS))
-            w.writeheader()
-            w.writerows(rows)
+        write_csv(summary, SUMMARY_COLUMNS, rows)
         log(f"[INFO] Saved finetune summary: {summary}")
     return {"rows": rows, "checkpoints": ckpts, "model": model, "optimizer": optimizer, "save_dir": save_dir,
             "config": cfg}

@@ -93,6 +93,39 @@ def test_evaluate_topk_matches_accuracy_topk(fresh):
     assert R.evaluate_topk(model, [], DEV) == (0.0, 0.0)
 
 
+def test_shared_evaluate_caps_k_at_the_class_count(fresh):
+    """driver.evaluate over three batches of 2 clips with topk=(1, 3, 5) against
+    finetune.accuracy_topk with (1, 3, 4), batch-weighted, to 1e-12: with 4 classes key 5 holds
+    the k = 4 value.  Labels by rank, so that every k has hits and k = 1, 3 have misses."""
+    from ssl_mae_amd import run_federated as R
+    from ssl_mae_amd.driver import evaluate
+    from ssl_mae_amd.finetune import accuracy_topk
+    from ssl_mae_amd.init_rule import synthetic_clip
+    model0, batches = fresh
+    model = copy.deepcopy(model0).eval()
+    clips = [clip for clip, _ in batches] + [torch.from_numpy(synthetic_clip(B, T, S, seed=72)).to(DEV)]
+    with torch.no_grad():
+        logits = [model(clip).float() for clip in clips]
+    srt = torch.cat(logits).sort(dim=1).values
+    assert bool((srt[:, 1:] - srt[:, :-1] > 0).all())             # no ties
+    order = torch.cat(logits).argsort(dim=1, descending=True)
+    labels = order[torch.arange(3 * B), torch.tensor([0, 3, 2, 1, 3, 0], device=DEV)]   # the label's rank per clip
+    loader = [(clip, labels[i * B:(i + 1) * B]) for i, clip in enumerate(clips)]
+    got = evaluate(model, loader, DEV, topk=(1, 3, 5))
+    want = {k: 0.0 for k in (1, 3, 4)}
+    for lg, (_, y) in zip(logits, loader):
+        acc = accuracy_topk(lg, y, topk=(1, 3, 4))
+        for k in want:
+            want[k] += acc[k] * y.size(0)
+    want = {k: v / (3 * B) for k, v in want.items()}
+    print(f"driver.evaluate {got}, accuracy_topk {want}")
+    assert sorted(got) == [1, 3, 5]
+    assert abs(got[1] - want[1]) <= 1e-12 and abs(got[3] - want[3]) <= 1e-12 and abs(got[5] - want[4]) <= 1e-12
+    assert (want[1], want[3], want[4]) == (2 / 6, 4 / 6, 1.0)
+    assert R.evaluate_topk(model, loader, DEV) == (got[1], got[5])
+    assert not model.training
+
+
 def _config(tmp_path, name, exchange):
     cfg = {"dataset": {"num_classes": NC, "clip_len": T, "image_size": S},
            "federated": {"num_clients": 3, "rounds": 2, "local_epochs": 1, "batch_size": 2, "exchange": exchange,
