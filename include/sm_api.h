@@ -676,6 +676,39 @@ int sm_fedavg_exchange(int num_src, const int32_t* src_models, const float* weig
 int sm_fedavg_exchange_counters(int num_src, const int32_t* src_models, int num_dst, const int32_t* dst_models,
                                 const void* table, int64_t table_bytes, hipStream_t st);
 
+/* ---- DP-FedAvg round exchange (McMahan et al. 2018; not in the reference) over the fp32 FedAvg
+ * exchange table above: every source's update x_c - theta is clipped to an L2 bound, the clipped
+ * updates are averaged onto theta and Gaussian noise is added; the result goes into every dst model.
+ * src_models, weights (already normalised) and dst_models are HOST arrays as for sm_fedavg_exchange;
+ * global_model is theta's model index and may be a destination.  seg_clip (DEVICE, one byte per
+ * segment of the table): 1 = clipped and noised, 0 = sm_fedavg_exchange's plain weighted sum of the
+ * sources, bit for bit.  stats (DEVICE, float [2 num_src]) receives norm_c, then scale_c.
+ * Three launches, no atomics, no host synchronise beyond the header read:
+ *   norms     norm_c = sqrt(sum over the clipped segments' elements of (x_c[i] - theta[i])^2): the
+ *             fp32 differences squared, a lane adding at most 8 of them (one chunk's share) in fp32,
+ *             everything above a lane in fp64 in a fixed order -- the same bits on every call
+ *   finalise  scale_c = min(1, clip_norm / (norm_c + 1e-6f)) in fp32 on the device (the form of
+ *             sm_grad_clip's coefficient; a non-finite norm_c goes through the same expression),
+ *             ws_c = fmul_rn(weights[c], scale_c)
+ *   update    clipped segment s, element i: acc = theta[i]; in src order acc = fadd_rn(acc,
+ *             fmul_rn(ws_c, fsub_rn(x_c[i], theta[i]))); then, when noise_std > 0,
+ *             acc = fmaf(noise_std, n, acc) with n sm_privacy_perturb's Gaussian of (seed, row = s,
+ *             column = i)
+ * A lane loads its elements from theta and every source before its first store, so destinations
+ * may alias sources and theta.  A chunk moves as 16-byte vectors when it is 16-byte aligned in every
+ * model of the launch, else element by element, with the same bits.
+ * Workspace sm_fedavg_dp_exchange_workspace_bytes (-1 for a bad count), 16-byte aligned.
+ * Returns -2 as sm_fedavg_exchange does, and for NULL weights / seg_clip / stats, global_model
+ * outside [0, P), clip_norm <= 0 or NaN, noise_std < 0 or NaN, a clipped segment of more than 2^32
+ * elements (the draw's column is 32 bits; the lengths are read back only from a table large enough
+ * to hold such a segment) or more than 2^32 segments; -4 for a NULL, short or misaligned workspace.
+ * Nothing is written in either case. */
+int64_t sm_fedavg_dp_exchange_workspace_bytes(int num_src, int64_t num_chunks);
+int sm_fedavg_dp_exchange(int num_src, const int32_t* src_models, const float* weights, int global_model,
+                          int num_dst, const int32_t* dst_models, const void* table, int64_t table_bytes,
+                          const uint8_t* seg_clip, float clip_norm, float noise_std, uint64_t seed, float* stats,
+                          void* ws, int64_t ws_bytes, hipStream_t st);
+
 /* ---- clip input pipeline (src/train_ssl_mae.py:137-141 PILToTensor + ConvertImageDtype +
  * Normalize; src/datasets/mae_loader.py:70-77 BGR swap img[[2,1,0]] and [C,T,H,W] stack).
  * frames uint8 [B][T][H][W][3] (decoded RGB) -> out fp32 [B][3][T][H][W],

@@ -19,6 +19,10 @@
   (torch.optim.AdamW against optim.GroupedAdamW) and one epoch of configs/finetune.yaml (see
   `finetune`).
 
+* `aux_bench.py fed_dp [--out profiles/fed_dp.txt]`: the DP-FedAvg aggregation
+  (FedCohort.aggregate_dp, three launches) against the plain aggregate and the eager
+  dp_aggregate_reference in the same process, with each launch's time and bandwidth (see `fed_dp`).
+
 Prints one JSON line per kernel; run under rocprofv3 --kernel-trace --stats to
 cross-check the average launch durations."""
 import json
@@ -296,6 +300,121 @@ def fedround(out_path=None, reps=5, rounds=5, num_classes=101):
             f.write(text)
 
 
+def _kernel_times(fn, reps, names):
+    """{name: ms per call} of the device kernels whose name contains one of `names`, from
+    torch.profiler's trace of `reps` calls."""
+    from torch.profiler import ProfilerActivity, profile
+    fn()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+    out = dict.fromkeys(names, 0.0)
+    for e in prof.key_averages():
+        if not str(getattr(e, "device_type", "")).endswith("CUDA"):
+            continue
+        us = getattr(e, "device_time_total", None)
+        us = getattr(e, "cuda_time_total", 0.0) if us is None else us
+        for n in names:
+            if n in e.key:
+                out[n] += float(us) / 1e3 / reps
+    return out
+
+
+def fed_dp(out_path=None, reps=5, rounds=5, num_classes=101):
+    """The DP-FedAvg aggregation over VideoClassifier models at 112^2 that have each run one forward,
+    K = 4 and K = 8 selected clients, clip_norm 1 and noise multiplier 1: FedCohort.aggregate_dp
+    (norms, finalise, update: three launches plus the counter launch) with and without noise, the
+    plain FedCohort.aggregate, and the eager dp_aggregate_reference over state_dicts, alternating in
+    one process.  The three launches' own times come from torch.profiler's trace of the same
+    calls; GB/s against algorithmic bytes, (K + 1) x 4 B per clipped element for the norms and
+    (K + 2) x 4 B per fp32 element for the update ((K + 1) x 4 B for the plain aggregate).  Ends
+    with the 4.9 GB copy calibration."""
+    import statistics
+    from ssl_mae_amd.finetune import VideoClassifier
+    lines = [f"device: {torch.cuda.get_device_name(0)}; VideoClassifier({num_classes}) at 112^2; {rounds} rounds of "
+             f"{reps} aggregations ({max(1, reps // 2)} for the eager reference), median [min .. max]"]
+    clip = torch.randn(1, 3, 1, 112, 112, device="cuda")
+    models = []
+    for s in range(9):
+        torch.manual_seed(s)
+        m = VideoClassifier(num_classes, img_size=112).cuda().eval()
+        with torch.no_grad():
+            m(clip)
+        models.append(m)
+    glob = models[0]
+    kernels = ("dp_norms_kernel", "dp_finalise_kernel", "dp_update_kernel")
+    results = []
+    for k in (4, 8):
+        clients = models[1:k + 1]
+        sel = list(range(k))
+        sizes = [100.0 + 10 * i for i in sel]
+        cohort = F.FedCohort(glob, clients)
+        n_all = sum(glob.state_dict()[key].numel() for key in cohort.float_keys)
+        n_clip = sum(glob.state_dict()[key].numel() for key, m in zip(cohort.float_keys, cohort._clip_modes) if m)
+        seed = F.dp_round_seed(42, 1)
+
+        def dp_noise():
+            cohort.aggregate_dp(sel, sizes, 1.0, 1.0, seed)
+
+        def dp_clean():
+            cohort.aggregate_dp(sel, sizes, 1.0, 0.0, seed)
+
+        def plain():
+            cohort.aggregate(sel, sizes)
+
+        def reference():
+            states = [{n: v.detach() for n, v in c.state_dict().items()} for c in clients]
+            F.dp_aggregate_reference(glob, states, sizes, 1.0, 1.0, seed)
+
+        for fn in (dp_noise, dp_clean, plain, reference):
+            fn()
+        torch.cuda.synchronize()
+        td, tc, tp, tr = [], [], [], []
+        for _ in range(rounds):                         # alternate the paths
+            td += _rounds(dp_noise, reps, 1)
+            tc += _rounds(dp_clean, reps, 1)
+            tp += _rounds(plain, reps, 1)
+            tr += _rounds(reference, max(1, reps // 2), 1)
+        md, mr = statistics.median(td), statistics.median(tr)
+        gb1, gb2, gbp = (k + 1) * 4 * n_clip / 1e9, (k + 2) * 4 * n_all / 1e9, (k + 1) * 4 * n_all / 1e9
+        lines.append(f"K={k} selected clients, {len(cohort.float_keys)} fp32 entries ({sum(cohort._clip_modes)} clipped), "
+                     f"{n_all} fp32 elements ({n_clip} clipped) per model:")
+        lines.append(f"  FedCohort.aggregate_dp, noise multiplier 1: {_fmt(td)}")
+        lines.append(f"  FedCohort.aggregate_dp, noise multiplier 0: {_fmt(tc)}")
+        lines.append(f"  FedCohort.aggregate (plain FedAvg): {_fmt(tp)}")
+        lines.append(f"  dp_aggregate_reference (eager torch over state_dicts), noise multiplier 1: {_fmt(tr)}  "
+                     f"{mr / md:.1f}x aggregate_dp")
+        try:
+            for label, fn in (("noise multiplier 1", dp_noise), ("noise multiplier 0", dp_clean)):
+                kt = _kernel_times(fn, reps, kernels)
+                lines.append(f"  launches, {label}: norms {kt[kernels[0]]:.3f} ms ({gb1:.3f} GB, "
+                             f"{gb1 / max(kt[kernels[0]], 1e-9) * 1e3:.0f} GB/s), finalise {kt[kernels[1]]:.3f} ms, update "
+                             f"{kt[kernels[2]]:.3f} ms ({gb2:.3f} GB, {gb2 / max(kt[kernels[2]], 1e-9) * 1e3:.0f} GB/s)")
+            tk = _kernel_times(plain, reps, ("fedavg_exchange_kernel",))["fedavg_exchange_kernel"]
+            plain_gbs = gbp / max(tk, 1e-9) * 1e3
+            lines.append(f"  launch of the plain aggregate: {tk:.3f} ms ({gbp:.3f} GB, {plain_gbs:.0f} GB/s)")
+        except Exception as exc:  # the trace splits the total; the totals above are the measurement
+            plain_gbs = float("nan")
+            lines.append(f"  launches: not measured ({type(exc).__name__}: {exc})")
+        results.append((k, md, mr, plain_gbs))
+        assert cohort.rebuilds == 1
+    del models, clients, cohort
+    torch.cuda.empty_cache()
+    line, copy_gbs = _copy_calibration(rounds)
+    lines.append(line)
+    for k, md, mr, gp in results:
+        lines.append(f"K={k}: plain aggregate launch at {gp / copy_gbs:.2f} of the copy calibration's bandwidth; aggregate_dp is "
+                     f"{'FASTER' if md < mr else 'NOT faster'} than dp_aggregate_reference ({md:.3f} ms against {mr:.3f} ms)")
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+
+
 def _count_launches(fn):
     """Device kernels / memsets / copies of one call, from torch.profiler's trace."""
     from torch.profiler import ProfilerActivity, profile
@@ -419,9 +538,9 @@ def finetune(out_path=None, reps=10, rounds=7, num_classes=101):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] in ("resize", "fedround", "finetune"):
+    if len(sys.argv) > 1 and sys.argv[1] in ("resize", "fedround", "finetune", "fed_dp"):
         out = sys.argv[3] if len(sys.argv) > 3 and sys.argv[2] == "--out" else None
-        {"resize": resize, "fedround": fedround, "finetune": finetune}[sys.argv[1]](out)
+        {"resize": resize, "fedround": fedround, "finetune": finetune, "fed_dp": fed_dp}[sys.argv[1]](out)
     else:
         main()
         frames()

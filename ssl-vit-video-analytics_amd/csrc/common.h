@@ -282,6 +282,31 @@ SM_DEV bool drop_keep_bits16(uint32_t h, uint32_t col, uint32_t thr) {
   return ((h >> ((col & 1) * 16)) & 0xFFFFu) >= thr;
 }
 
+// Counter-based perturbation draws (csrc/privacy.hip's feature noise and masks, csrc/fed_dp.hip's
+// DP-FedAvg noise): three 32-bit streams per (seed, row, col); the row and the column go through
+// separate fmix32 rounds: rb = fmix32(seed32 + row * 0x9E3779B1) is a bijection of the row,
+// rk_k = fmix32(rb + K_k) its three stream keys, h_k = fmix32(rk_k + col * 0x7FEB352D) a bijection
+// of the column within a row.  Two elements share (h0, h1) only if two independent 32-bit
+// conditions hold.  Streams 0 and 1 make the Gaussian, stream 2 the mask.
+constexpr uint32_t kRowMul = 0x9E3779B1u, kColMul = 0x7FEB352Du;
+constexpr uint32_t kStream0 = 0x68E31DA4u, kStream1 = 0xB5297A4Du, kStream2 = 0x1B56C4E9u;
+
+struct RowKeys {
+  uint32_t k0, k1, k2;
+};
+SM_DEV RowKeys row_keys(uint32_t s32, uint32_t row) {
+  const uint32_t rb = fmix32(s32 + row * kRowMul);
+  return RowKeys{fmix32(rb + kStream0), fmix32(rb + kStream1), fmix32(rb + kStream2)};
+}
+// Standard normal of (row keys, cm = col * kColMul): Box-Muller's cosine branch (the sine branch is
+// not used) on u1 in (0, 1] and 2 u2 in [0, 2), both exact in fp32.
+SM_DEV float gauss_draw(const RowKeys& rk, uint32_t cm) {
+  const uint32_t h0 = fmix32(rk.k0 + cm), h1 = fmix32(rk.k1 + cm);
+  const float u1 = (float)((h0 >> 8) + 1u) * 0x1p-24f;      // (0, 1], exact
+  const float u2x2 = (float)(h1 >> 8) * 0x1p-23f;           // 2 u2 in [0, 2), exact
+  return sqrtf(-2.0f * logf(u1)) * cospif(u2x2);            // cos(2 pi u2)
+}
+
 // Reduce partial slabs part[nb][ncols] over nb.  Block = 32 columns x 8 row groups;
 // fp64 accumulation, fixed order (deterministic).  Writes fp64 (outd) and/or
 // fp32 (outf, optionally accumulating).

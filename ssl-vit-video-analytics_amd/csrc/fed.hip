@@ -12,14 +12,15 @@
 // rounding of w_i / total_w.  The result is therefore bit-identical to
 // fedavg_aggregate's.
 #include "common.h"
+#include "fed_table.h"
 #include "sm_api.h"
+
+using namespace fedtab;   // the table view and the argument check, shared with fed_dp.hip
 
 // The reference rounds x * w and acc + (x * w) separately: this file is compiled
 // with -ffp-contract=off (build.py FILE_FLAGS) so no FMA is formed.
 
 namespace {
-
-constexpr int kMaxClients = SM_FEDAVG_MAX_CLIENTS;
 
 struct ClientPtrs {
   const float* p[kMaxClients];
@@ -81,47 +82,8 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 // Sources and destinations may alias (in-place aggregation): a lane loads its elements
 // from every source before its first store, lanes own disjoint elements, and no pointer
 // here is __restrict__.
-constexpr int kChunk = SM_FEDAVG_CHUNK_ELEMS;
 constexpr int kVecPerLane = kChunk / (256 * 4);   // float4 groups per lane per source
 static_assert(kChunk % 1024 == 0, "a chunk is a whole number of 256-lane float4 rows");
-
-struct ExchangeArgs {
-  int32_t src[kMaxClients];
-  float w[kMaxClients];
-  int32_t dst[kMaxClients + 1];
-  int num_src, num_dst;
-};
-
-struct TableView {
-  int64_t S, C;
-  const uint64_t* addr;      // [P][S]
-  const int64_t* seg_len;    // [S]
-  const int64_t* chunk_off;  // [C]
-  const int32_t* chunk_seg;  // [C]
-};
-
-SM_DEV TableView table_view(const unsigned char* tab) {
-  const SmFedTableHeader* h = (const SmFedTableHeader*)tab;
-  TableView t;
-  t.S = h->num_segments;
-  t.C = h->num_chunks;
-  t.addr = (const uint64_t*)(tab + sizeof(SmFedTableHeader));
-  t.seg_len = (const int64_t*)(t.addr + h->num_models * t.S);
-  t.chunk_off = t.seg_len + t.S;
-  t.chunk_seg = (const int32_t*)(t.chunk_off + t.C);
-  return t;
-}
-
-// Elements [off, off + n) of segment `seg`: false when the chunk entry points outside it.
-SM_DEV bool chunk_range(const TableView& t, int64_t c, int64_t& seg, int64_t& off, int64_t& n) {
-  seg = t.chunk_seg[c];
-  off = t.chunk_off[c];
-  if (seg < 0 || seg >= t.S || off < 0) return false;
-  const int64_t len = t.seg_len[seg];
-  if (off >= len) return false;
-  n = len - off < kChunk ? len - off : kChunk;
-  return true;
-}
 
 // KC > 0: source count known at compile time (all KC * kVecPerLane loads of a lane are issued
 // before the first multiply-add); KC == 0: runtime count.  COPY: one source, stored as loaded.
@@ -233,40 +195,6 @@ __global__ void __launch_bounds__(256) fedavg_exchange_counters_kernel(ExchangeA
   }
 }
 
-// Counts, model indices and the table's header (read back from the device: 64 bytes, once
-// per launch) against table_bytes and the entry point's element size.  0, or -2.
-int exchange_args(int num_src, const int32_t* src_models, const float* weights, int num_dst,
-                  const int32_t* dst_models, const void* table, int64_t table_bytes, int elem_bytes,
-                  hipStream_t st, ExchangeArgs& a, int64_t& chunks) {
-  if (num_src < 1 || num_src > kMaxClients || num_dst < 1 || num_dst > kMaxClients + 1) return -2;
-  if (!src_models || !dst_models || !table || table_bytes < (int64_t)sizeof(SmFedTableHeader)) return -2;
-  SmFedTableHeader h;
-  hipError_t e = hipMemcpyAsync(&h, table, sizeof(h), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return (int)e;
-  if (h.magic != SM_FEDAVG_TABLE_MAGIC || h.elem_bytes != elem_bytes || h.chunk_elems != kChunk) return -2;
-  if (h.num_models < 1 || h.num_models > kMaxClients + 1 || h.num_segments < 0 || h.num_chunks < 0) return -2;
-  if (h.num_segments > (int64_t)1 << 31 || h.num_chunks > (int64_t)1 << 40) return -2;
-  int64_t bytes = (int64_t)sizeof(SmFedTableHeader) + 8 * h.num_models * h.num_segments + 8 * h.num_segments +
-                  12 * h.num_chunks;
-  bytes = (bytes + 15) / 16 * 16;
-  if (h.total_bytes != bytes || table_bytes != bytes) return -2;
-  a = ExchangeArgs{};
-  for (int j = 0; j < num_src; ++j) {
-    if (src_models[j] < 0 || src_models[j] >= h.num_models) return -2;
-    a.src[j] = src_models[j];
-    a.w[j] = weights ? weights[j] : 0.f;
-  }
-  for (int d = 0; d < num_dst; ++d) {
-    if (dst_models[d] < 0 || dst_models[d] >= h.num_models) return -2;
-    a.dst[d] = dst_models[d];
-  }
-  a.num_src = num_src;
-  a.num_dst = num_dst;
-  chunks = h.num_chunks;
-  return 0;
-}
-
 }  // namespace
 
 extern "C" int sm_fedavg_exchange(int num_src, const int32_t* src_models, const float* weights, int num_dst,
@@ -274,8 +202,9 @@ extern "C" int sm_fedavg_exchange(int num_src, const int32_t* src_models, const 
                                   hipStream_t st) {
   if (copy_only ? num_src != 1 : !weights) return -2;
   ExchangeArgs a;
-  int64_t chunks = 0;
-  const int rc = exchange_args(num_src, src_models, weights, num_dst, dst_models, table, table_bytes, 4, st, a, chunks);
+  SmFedTableHeader h{};
+  const int rc = exchange_args(num_src, src_models, weights, num_dst, dst_models, table, table_bytes, 4, st, a, h);
+  const int64_t chunks = h.num_chunks;
   if (rc != 0 || chunks == 0) return rc;
   // 8 resident 256-lane blocks per CU on 256 CUs, grid-stride over chunks beyond that.
   const dim3 g((unsigned)(chunks < 2048 ? chunks : 2048)), b(256);
@@ -300,8 +229,9 @@ extern "C" int sm_fedavg_exchange_counters(int num_src, const int32_t* src_model
                                            const int32_t* dst_models, const void* table, int64_t table_bytes,
                                            hipStream_t st) {
   ExchangeArgs a;
-  int64_t chunks = 0;
-  const int rc = exchange_args(num_src, src_models, nullptr, num_dst, dst_models, table, table_bytes, 8, st, a, chunks);
+  SmFedTableHeader h{};
+  const int rc = exchange_args(num_src, src_models, nullptr, num_dst, dst_models, table, table_bytes, 8, st, a, h);
+  const int64_t chunks = h.num_chunks;
   if (rc != 0 || chunks == 0) return rc;
   hipLaunchKernelGGL(fedavg_exchange_counters_kernel, dim3((unsigned)(chunks < 2048 ? chunks : 2048)), dim3(256), 0,
                      st, a, (const unsigned char*)table);

@@ -18,39 +18,20 @@ namespace {
 constexpr int kThreads = 256;
 
 // ---------------------------------------------------------------- perturbation draws
-// Three 32-bit streams per (seed, row, col); the row and the column go through separate fmix32
-// rounds: rb = fmix32(seed32 + row * 0x9E3779B1) is a bijection of the row, rk_k = fmix32(rb + K_k)
-// its three stream keys, h_k = fmix32(rk_k + col * 0x7FEB352D) a bijection of the column within a
-// row.  Two elements share (h0, h1) only if two independent 32-bit conditions hold.
-constexpr uint32_t kRowMul = 0x9E3779B1u, kColMul = 0x7FEB352Du;
-constexpr uint32_t kStream0 = 0x68E31DA4u, kStream1 = 0xB5297A4Du, kStream2 = 0x1B56C4E9u;
-
+// The streams, their keys (row_keys) and the Gaussian (gauss_draw) are csrc/common.h's counter-based
+// perturbation draws, shared with csrc/fed_dp.hip.
 struct PerturbCfg {
   uint64_t thr[SM_PRIVACY_MAX_CONFIGS];   // keep iff (uint64)h2 >= thr; 0 keeps all, 2^32 drops all
   float sigma[SM_PRIVACY_MAX_CONFIGS];
   uint32_t s32[SM_PRIVACY_MAX_CONFIGS];
 };
 
-struct RowKeys {
-  uint32_t k0, k1, k2;
-};
-SM_DEV RowKeys row_keys(uint32_t s32, uint32_t row) {
-  const uint32_t rb = fmix32(s32 + row * kRowMul);
-  return RowKeys{fmix32(rb + kStream0), fmix32(rb + kStream1), fmix32(rb + kStream2)};
-}
-
 // One element: noise first, then the 0/1 mask without a 1 / keep rescale (feature_noise.py:4-15).
 // sigma <= 0 and thr == 0 leave the value untouched (bit-exact).
 SM_DEV float perturb_one(float z, const RowKeys& rk, uint32_t col, float sigma, uint64_t thr) {
   const uint32_t cm = col * kColMul;
   float v = z;
-  if (sigma > 0.f) {
-    const uint32_t h0 = fmix32(rk.k0 + cm), h1 = fmix32(rk.k1 + cm);
-    const float u1 = (float)((h0 >> 8) + 1u) * 0x1p-24f;      // (0, 1], exact
-    const float u2x2 = (float)(h1 >> 8) * 0x1p-23f;           // 2 u2 in [0, 2), exact
-    const float n = sqrtf(-2.0f * logf(u1)) * cospif(u2x2);   // cos(2 pi u2); the sine branch is not used
-    v = fmaf(sigma, n, z);
-  }
+  if (sigma > 0.f) v = fmaf(sigma, gauss_draw(rk, cm), z);
   if (thr != 0) {
     const uint32_t h2 = fmix32(rk.k2 + cm);
     v *= (uint64_t)h2 >= thr ? 1.0f : 0.0f;

@@ -24,8 +24,10 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", CSRC, "-I
 # `#pragma clang fp contract`, so contraction is switched off for that file.  temporal.hip's
 # 16-byte and scalar forms must round alike: its fmas are explicit, nothing else may fuse.
 # resize.hip's interpolation is matched bit for bit by a host mirror: one explicit fma, no other.
+# fed_dp.hip's clipped update is matched operation by operation by a host mirror too, and its
+# plain segments repeat fed.hip's arithmetic: the noise's explicit fma is its only one.
 FILE_FLAGS = {"fed.hip": ["-ffp-contract=off"], "temporal.hip": ["-ffp-contract=off"],
-              "resize.hip": ["-ffp-contract=off"],
+              "resize.hip": ["-ffp-contract=off"], "fed_dp.hip": ["-ffp-contract=off"],
               "attention.hip": ["-fno-slp-vectorize"], "gemm.hip": ["-fno-slp-vectorize"]}
 
 

@@ -18,6 +18,12 @@ client states are staged into device buffers and the result stays on the global
 model's device.  The flattening (one torch.cat per client) is data movement; the
 arithmetic is the HIP kernel — there is no CPU arithmetic path.
 
+DP-FedAvg (not in the reference): `FedCohort.aggregate_dp` clips every client's update over the
+global model's parameters, averages the clipped updates and adds Gaussian noise in three launches
+(sm_fedavg_dp_exchange); `dp_aggregate_reference` is the same in eager torch, `dp_aggregate_mirror`
+the numpy statement the tests compare bits with, `dp_epsilon` the RDP accountant's estimate.
+BatchNorm running statistics keep plain FedAvg and are outside the guarantee.
+
 Multi-GPU (BASELINE config C5, 4 clients on 4 GPUs): `fedavg_allgather` makes
 every rank one client.  Each rank's flat fp32 state is all-gathered over RCCL
 (one collective per round, (N-1) x 80 MiB per rank over xGMI ~ 2 ms at N=4),
@@ -28,12 +34,15 @@ per round).  Counters take a MAX all-reduce; other integer buffers come from
 rank 0 (the "first client").
 """
 import functools
+import math
 import random
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
 from . import ops as K    # every kernel launch through the torch.ops.ssl_mae dispatcher
+from .privacy import _COL_MUL, _ROW_MUL, _STREAMS, config_seed
 from .utils import log_line
 
 
@@ -188,6 +197,11 @@ class FedCohort:
         if any([k for k, _, _ in sl] != list(ref) for sl in self._slots):
             raise RuntimeError("[ERROR] FedCohort: a model's state_dict() is not its modules' parameters and "
                                "persistent buffers (state_dict hooks are not supported)")
+        # the DP exchange clips the global model's parameters; float buffers (BatchNorm running
+        # statistics) keep plain FedAvg
+        params = {k for k, _ in global_model.named_parameters(remove_duplicate=False)}
+        self._clip_modes = [1 if k in params else 0 for k in self.float_keys]
+        self._float_chunks = sum(-(-ref[k].numel() // K.FEDAVG_CHUNK_ELEMS) for k in self.float_keys)
         self.rebuilds = 0
         self._build()
 
@@ -200,6 +214,7 @@ class FedCohort:
             [[e[k].detach() for k in self.float_keys] for e in ents], torch.float32)
         self._count_table, self._count_addr = K.fedavg_exchange_table(
             [[e[k].detach() for k in self.count_keys] for e in ents], torch.int64)
+        self._seg_clip = torch.tensor(self._clip_modes, dtype=torch.uint8).to(self._float_table.device)
         self.rebuilds += 1
 
     def _fresh(self, p, ents):
@@ -209,13 +224,23 @@ class FedCohort:
                         for k, a in zip(self.count_keys, self._count_addr[p * nc:(p + 1) * nc])))
 
     @torch.no_grad()
-    def exchange(self, src, weights, dst, copy_only=False):
+    def exchange(self, src, weights, dst, copy_only=False, dp=None):
         """Table-model indices: sources (in accumulation order), their normalised fp32 weights,
-        destinations."""
-        ents = {p: self._entries(p) for p in dict.fromkeys(list(src) + list(dst))}
+        destinations.  dp = (clip_norm, noise_std, seed): the fp32 entries go through
+        sm_fedavg_dp_exchange against the global model (table model 0) instead, and the device
+        `stats` tensor (the sources' update norms, then their clip scales) is returned."""
+        ents = {p: self._entries(p) for p in dict.fromkeys(list(src) + list(dst) + ([0] if dp else []))}
         if not all(self._fresh(p, e) for p, e in ents.items()):
             self._build()
-        if self.float_keys:
+        stats = None
+        if dp is not None:
+            if not self.float_keys:
+                raise RuntimeError("[ERROR] FedCohort: DP-FedAvg needs fp32 state entries")
+            clip_norm, noise_std, seed = dp
+            stats = K.fedavg_dp_exchange([ents[p][k].detach() for p in dst for k in self.float_keys], src, weights, 0,
+                                         dst, self._float_table, self._float_chunks, self._seg_clip, clip_norm,
+                                         noise_std, seed)
+        elif self.float_keys:
             K.fedavg_exchange([ents[p][k].detach() for p in dst for k in self.float_keys], src, weights, dst,
                               self._float_table, copy_only)
         if self.count_keys:
@@ -225,6 +250,22 @@ class FedCohort:
             for p in dst:
                 if p != src[0]:
                     ents[p][k].copy_(ents[src[0]][k])
+        return stats
+
+    def aggregate_dp(self, selected, client_weights, clip_norm, noise_multiplier, seed, also=()):
+        """DP-FedAvg (McMahan et al. 2018) of the clients `selected` into the global model and the
+        clients `also`: each client's update x_c - theta over the global model's parameters is
+        clipped to the L2 bound `clip_norm`, the clipped updates are averaged onto theta with the
+        normalised weights, and noise_multiplier * clip_norm * max(weight) -- the noise multiplier
+        times one client's sensitivity of the weighted sum -- times a standard Gaussian of (seed,
+        entry, element) is added, in three launches (sm_fedavg_dp_exchange).  Float buffers, the
+        BatchNorm running statistics, keep plain FedAvg and are OUTSIDE the guarantee, as are the
+        integer entries (num_batches_tracked: max; others: the first client's).
+        -> the device tensor fp32 [2 * len(selected)]: the update norms, then the clip scales."""
+        total_w = _check(selected, client_weights)
+        norm = _norm_weights(client_weights, total_w)
+        return self.exchange(self._clients(selected), norm, [0] + self._clients(also),
+                             dp=(float(clip_norm), dp_noise_std(norm, clip_norm, noise_multiplier), int(seed)))
 
     def aggregate(self, selected, client_weights, also=()):
         """FedAvg of the clients `selected` (in that order) into the global model and into the
@@ -243,6 +284,178 @@ class FedCohort:
             if not 0 <= int(c) < len(self.client_models):
                 raise RuntimeError(f"[ERROR] FedCohort: no client {c} (clients 0..{len(self.client_models) - 1})")
         return [int(c) + 1 for c in ids]
+
+
+# ------------------------------------------------------------------ DP-FedAvg (not in the reference)
+def dp_round_seed(seed, r):
+    """The noise seed of round r: privacy.config_seed(seed, r)."""
+    return config_seed(seed, r)
+
+
+def dp_noise_std(norm_weights, clip_norm, noise_multiplier):
+    """noise_multiplier x the L2 sensitivity of the weighted sum to one client, max(weight) x
+    clip_norm, formed on the host."""
+    return float(noise_multiplier) * float(clip_norm) * max(float(w) for w in norm_weights)
+
+
+def _dp_check(clip_norm, noise_multiplier):
+    if not float(clip_norm) > 0.0:
+        raise ValueError(f"[ERROR] DP-FedAvg: clip_norm must be > 0, got {clip_norm}")
+    if not float(noise_multiplier) >= 0.0:
+        raise ValueError(f"[ERROR] DP-FedAvg: noise_multiplier must be >= 0, got {noise_multiplier}")
+
+
+def _fmix32_t(h):
+    h = h & 0xFFFFFFFF
+    h = h ^ (h >> 16)
+    h = (h * 0x85EBCA6B) & 0xFFFFFFFF
+    h = h ^ (h >> 13)
+    h = (h * 0xC2B2AE35) & 0xFFFFFFFF
+    return h ^ (h >> 16)
+
+
+def dp_noise(seed, seg, n, device):
+    """The standard Gaussian of sm_privacy_perturb for row `seg`, columns 0..n-1, as fp64 torch
+    ops on `device` (privacy.perturb_draws / gaussian_from_draws, one row)."""
+    seed = int(seed) & ((1 << 64) - 1)
+    s32 = (seed & 0xFFFFFFFF) ^ (seed >> 32)
+    rb = _fmix32_t(torch.tensor((s32 + int(seg) * _ROW_MUL) & 0xFFFFFFFF, dtype=torch.int64, device=device))
+    cm = (torch.arange(n, dtype=torch.int64, device=device) * _COL_MUL) & 0xFFFFFFFF
+    h0, h1 = (_fmix32_t(_fmix32_t(rb + k) + cm) for k in _STREAMS[:2])
+    u1 = ((h0 >> 8) + 1).double() * 2.0 ** -24
+    u2 = (h1 >> 8).double() * 2.0 ** -24
+    return torch.sqrt(-2.0 * torch.log(u1)) * torch.cos(2.0 * math.pi * u2)
+
+
+def dp_aggregate_reference(global_model, client_states, client_weights, clip_norm, noise_multiplier, seed):
+    """DP-FedAvg in eager torch over state_dicts, the mathematics of FedCohort.aggregate_dp entry
+    by entry: the global model's float parameters are clipped and noised (the noise is the same
+    function of (seed, index among the float entries, element), added in fp64 and rounded once),
+    float buffers take fedavg_aggregate's weighted sum, num_batches_tracked the max, other integer
+    entries the first client's value.  Loads the result into `global_model` (strict) and returns
+    (the new state dict, the fp32 [2 K] tensor of update norms then clip scales).  It serves
+    `federated.exchange: reference` and is the baseline the fused exchange is timed against."""
+    _dp_check(clip_norm, noise_multiplier)
+    total_w = _check(client_states, client_weights)
+    norm = _norm_weights(client_weights, total_w)
+    noise_std = dp_noise_std(norm, clip_norm, noise_multiplier)
+    global_state = global_model.state_dict()
+    device = _device_of(global_model, global_state)
+    params = {k for k, _ in global_model.named_parameters(remove_duplicate=False)}
+    float_keys = [k for k, v in global_state.items() if _is_float_tensor(v)]
+    for k in float_keys:
+        if global_state[k].dtype != torch.float32 or any(k not in cs for cs in client_states):
+            raise RuntimeError(f"[ERROR] DP-FedAvg needs {k} as fp32 in every client state")
+    clipped = [k for k in float_keys if k in params]
+
+    sq = torch.zeros(len(client_states), dtype=torch.float64, device=device)
+    for c, cs in enumerate(client_states):
+        for k in clipped:
+            sq[c] += (cs[k].detach().to(device) - global_state[k].detach()).double().pow(2).sum()
+    norms = sq.sqrt().float()
+    scales = torch.clamp(float(clip_norm) / (norms + 1e-6), max=1.0)          # a NaN norm stays a NaN
+    ws = torch.tensor(norm, dtype=torch.float32, device=device) * scales
+
+    new_state = {}
+    for k, g in global_state.items():
+        if k in params and _is_float_tensor(g):
+            theta = g.detach()
+            acc = theta.clone()
+            for c, cs in enumerate(client_states):
+                acc += ws[c] * (cs[k].detach().to(device) - theta)
+            if noise_std > 0.0:
+                n = dp_noise(seed, float_keys.index(k), acc.numel(), device).view(acc.shape)
+                acc = (acc.double() + noise_std * n).float()
+            new_state[k] = acc
+        elif _is_float_tensor(g):
+            acc = torch.zeros_like(g.detach())
+            for cs, w in zip(client_states, norm):
+                acc += cs[k].detach().to(device) * w
+            new_state[k] = acc
+        elif any(k not in cs for cs in client_states):
+            new_state[k] = g.detach().clone()
+        elif "num_batches_tracked" in k:
+            new_state[k] = torch.stack([cs[k].detach().to(device) for cs in client_states]).max(dim=0).values
+        else:
+            new_state[k] = client_states[0][k].detach().to(device).clone()
+    global_model.load_state_dict(new_state, strict=True)
+    return new_state, torch.cat([norms, scales])
+
+
+def dp_aggregate_mirror(theta, sources, norm_weights, seg_clip, clip_norm, scales=None):
+    """Host mirror (numpy) of sm_fedavg_dp_exchange without its noise.  theta: S fp32 arrays;
+    sources: K lists of S fp32 arrays; norm_weights: the K normalised fp32 weights; seg_clip: S
+    modes.  -> (the S result arrays, the K update norms in fp64).  The update repeats the kernel's
+    pass 2 one operation at a time in np.float32 (add, subtract and multiply are correctly
+    rounded), with the clip `scales` it is given (fp32 [K], e.g. the device's own); None forms them
+    from the fp64 norms in fp32, min(1, clip_norm / (norm + 1e-6))."""
+    f32 = np.float32
+    theta = [np.asarray(t, dtype=f32) for t in theta]
+    sources = [[np.asarray(x, dtype=f32) for x in src] for src in sources]
+    norms = np.array([math.sqrt(sum(float(np.sum((x.astype(np.float64) - t.astype(np.float64)) ** 2))
+                                    for x, t, m in zip(src, theta, seg_clip) if m)) for src in sources])
+    if scales is None:
+        with np.errstate(invalid="ignore"):
+            scales = np.minimum(f32(1.0), f32(clip_norm) / (norms.astype(f32) + f32(1e-6)))
+    scales = np.asarray(scales, dtype=f32)
+    w = [f32(x) for x in norm_weights]
+    ws = [w[c] * scales[c] for c in range(len(sources))]
+    out = []
+    for s, (t, m) in enumerate(zip(theta, seg_clip)):
+        if m:
+            acc = t.copy()
+            for c, src in enumerate(sources):
+                acc = acc + ws[c] * (src[s] - t)
+        else:
+            acc = np.zeros_like(t)
+            for c, src in enumerate(sources):
+                acc = acc + src[s] * w[c]
+        out.append(acc)
+    return out, norms
+
+
+def dp_epsilon(noise_multiplier, sample_rate, rounds, delta, orders=range(2, 256)):
+    """An ESTIMATE of the (epsilon, delta) budget spent by `rounds` rounds of DP-FedAvg: the
+    Renyi-DP accountant of the sampled Gaussian mechanism at integer orders (Mironov, Talwar,
+    Zhang 2019, "Renyi Differential Privacy of the Sampled Gaussian Mechanism", eq. for integer
+    alpha), with z = noise_multiplier and q = sample_rate:
+
+        A_alpha = sum_{k=0..alpha} C(alpha, k) (1 - q)^(alpha - k) q^k exp((k^2 - k) / (2 z^2))
+        RDP_alpha = log(A_alpha) / (alpha - 1)
+        epsilon = min_alpha (rounds * RDP_alpha + log(1 / delta) / (alpha - 1))
+
+    in log space (lgamma, log-sum-exp).  inf for noise_multiplier == 0, 0 for rounds == 0.
+    What it assumes, and the driver does not strictly provide: clients are sampled independently
+    with probability q (Poisson sampling; the driver draws a fixed-size sample of
+    q = selected / num_clients), one client changes the weighted sum by at most max(weight) x
+    clip_norm (the weights come from the clients' sample counts, which are themselves data), and
+    only the clipped parameters count: the BatchNorm running statistics and the integer entries
+    are exchanged without clipping or noise and are outside the guarantee."""
+    z, q, T, delta = float(noise_multiplier), float(sample_rate), int(rounds), float(delta)
+    if z < 0.0 or not 0.0 <= q <= 1.0 or T < 0 or not 0.0 < delta < 1.0:
+        raise ValueError("[ERROR] dp_epsilon: noise_multiplier >= 0, 0 <= sample_rate <= 1, rounds >= 0, "
+                         "0 < delta < 1")
+    if T == 0:
+        return 0.0
+    if z == 0.0:
+        return math.inf
+    best = math.inf
+    for a in orders:
+        a = int(a)
+        terms = []
+        for k in range(a + 1):
+            if (q == 0.0 and k > 0) or (q == 1.0 and k < a):
+                continue                                   # a zero-probability term
+            t = math.lgamma(a + 1) - math.lgamma(k + 1) - math.lgamma(a - k + 1) + (k * k - k) / (2.0 * z * z)
+            if a - k:
+                t += (a - k) * math.log1p(-q)
+            if k:
+                t += k * math.log(q)
+            terms.append(t)
+        m = max(terms)
+        log_a = m + math.log(sum(math.exp(t - m) for t in terms))
+        best = min(best, T * log_a / (a - 1) + math.log(1.0 / delta) / (a - 1))
+    return best
 
 
 # ------------------------------------------------------------------ multi-GPU (C5)
@@ -329,11 +542,36 @@ def _round_record(log, r, selected, losses, global_state, top1, top5):
     return rec
 
 
+def _dp_round(log, r, rec, stats, selected, weights, dp):
+    """One read-back of the round's DP statistics: a non-finite update norm raises, naming the
+    client; the record gains dp_clipped / dp_norm_mean / dp_norm_max / dp_noise_std and the log one
+    line."""
+    vals = [float(x) for x in stats.tolist()]
+    k = len(selected)
+    norms, scales = vals[:k], vals[k:]
+    for cid, n in zip(selected, norms):
+        if not math.isfinite(n):
+            raise RuntimeError(f"[ERROR] Round {r}: the update of client {cid} has a non-finite norm ({n})")
+    rec["dp_clipped"] = int(sum(1 for s in scales if s < 1.0))
+    rec["dp_norm_mean"] = float(sum(norms) / k)
+    rec["dp_norm_max"] = float(max(norms))
+    rec["dp_noise_std"] = dp_noise_std(_norm_weights(weights, float(sum(weights))), dp["clip_norm"],
+                                       dp["noise_multiplier"])
+    log(f"[INFO] Round {r} dp_clipped={rec['dp_clipped']}/{k} dp_norm_mean={rec['dp_norm_mean']:.4f} "
+        f"dp_norm_max={rec['dp_norm_max']:.4f} dp_noise_std={rec['dp_noise_std']:.6f}")
+    return rec
+
+
 def run_fedavg(global_model, client_models, client_loaders, client_sizes, evaluate_fn, device, rounds=10,
-               client_fraction=1.0, amp=True, log_f=None):
+               client_fraction=1.0, amp=True, log_f=None, dp=None):
     """fed_loop.py:65-150: each round samples clients with random.Random(42),
     broadcasts the global weights, runs client_loaders[cid]["update_fn"](model),
-    aggregates with fedavg_aggregate and evaluates.  Returns the per-round records."""
+    aggregates with fedavg_aggregate and evaluates.  Returns the per-round records.
+    dp = {"clip_norm", "noise_multiplier", "seed"}: the round aggregates with
+    dp_aggregate_reference under dp_round_seed(seed, r) instead, and its record and log carry the
+    DP statistics (_dp_round)."""
+    if dp is not None:
+        _dp_check(dp["clip_norm"], dp["noise_multiplier"])
     num_clients = len(client_models)
     rng = random.Random(42)
     records = []
@@ -351,17 +589,26 @@ def run_fedavg(global_model, client_models, client_loaders, client_sizes, evalua
             losses.append(float(client_loaders[cid]["update_fn"](client_models[cid])))
             states.append({k: v.detach() for k, v in client_models[cid].state_dict().items()})
             weights.append(float(client_sizes[cid]))
-        new_state = fedavg_aggregate(global_model, states, weights)
+        if dp is None:
+            new_state = fedavg_aggregate(global_model, states, weights)
+        else:
+            new_state, stats = dp_aggregate_reference(global_model, states, weights, dp["clip_norm"],
+                                                      dp["noise_multiplier"], dp_round_seed(dp["seed"], r))
         top1, top5 = evaluate_fn(global_model)
         records.append(_round_record(log, r, selected, losses, new_state, top1, top5))
+        if dp is not None:
+            _dp_round(log, r, records[-1], stats, selected, weights, dp)
     return records
 
 
 def run_fedavg_fused(global_model, client_models, client_loaders, client_sizes, evaluate_fn, device, rounds=10,
-                     client_fraction=1.0, amp=True, log_f=None):
+                     client_fraction=1.0, amp=True, log_f=None, dp=None):
     """run_fedavg with the round's exchange through a FedCohort: the same sampled clients, log
     lines and records, and bit-identical model states, with one broadcast launch and one
-    aggregation launch per round in place of the state_dict copies."""
+    aggregation launch per round in place of the state_dict copies.  With `dp` (as run_fedavg's)
+    the aggregation is FedCohort.aggregate_dp."""
+    if dp is not None:
+        _dp_check(dp["clip_norm"], dp["noise_multiplier"])
     num_clients = len(client_models)
     rng = random.Random(42)
     records = []
@@ -374,7 +621,14 @@ def run_fedavg_fused(global_model, client_models, client_loaders, client_sizes, 
         log(f"[INFO] Round {r}/{rounds} selected_clients={selected}")
         cohort.broadcast(selected)
         losses = [float(client_loaders[cid]["update_fn"](client_models[cid])) for cid in selected]
-        cohort.aggregate(selected, [float(client_sizes[cid]) for cid in selected])
+        weights = [float(client_sizes[cid]) for cid in selected]
+        if dp is None:
+            cohort.aggregate(selected, weights)
+        else:
+            stats = cohort.aggregate_dp(selected, weights, dp["clip_norm"], dp["noise_multiplier"],
+                                        dp_round_seed(dp["seed"], r))
         top1, top5 = evaluate_fn(global_model)
         records.append(_round_record(log, r, selected, losses, global_model.state_dict(), top1, top5))
+        if dp is not None:
+            _dp_round(log, r, records[-1], stats, selected, weights, dp)
     return records

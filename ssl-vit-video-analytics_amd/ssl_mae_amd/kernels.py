@@ -1132,6 +1132,41 @@ def fedavg_exchange_counters(src_models, dst_models, table):
     _fedavg_exchange_call("fedavg_exchange_counters", src_models, None, dst_models, table, [])
 
 
+def fedavg_dp_exchange(src_models, weights, global_model, dst_models, table, num_chunks, seg_clip, clip_norm,
+                       noise_std, seed, stats=None, ws=None):
+    """DP-FedAvg over an fp32 cohort table (sm_fedavg_dp_exchange, include/sm_api.h): the sources'
+    updates against model `global_model`, clipped to `clip_norm` over the segments whose `seg_clip`
+    byte is 1, averaged with the normalised `weights` onto it, plus noise_std x the counter Gaussian
+    of (seed, segment, element); segments with byte 0 get the plain weighted sum.  The result goes
+    into every destination model.  `num_chunks` is the table's chunk count (it sizes the
+    workspace); seg_clip is a uint8 device tensor with one byte per segment of the table.
+    -> stats, fp32 [2 * sources] on the device: the update norms, then the clip scales."""
+    import ctypes
+    _chk(table, seg_clip, stats, ws)
+    if table.dtype != torch.uint8 or not table.is_contiguous():
+        raise _lib.KernelError("fedavg_dp_exchange: the table is a contiguous uint8 device tensor "
+                               "(fedavg_exchange_table)")
+    if len(weights) != len(src_models):
+        raise _lib.KernelError(f"fedavg_dp_exchange: {len(src_models)} sources but {len(weights)} weights")
+    if seg_clip is not None and (seg_clip.dtype != torch.uint8 or not seg_clip.is_contiguous()):
+        raise _lib.KernelError("fedavg_dp_exchange: seg_clip is a contiguous uint8 device tensor")
+    k = len(src_models)
+    if stats is None:
+        stats = torch.empty(2 * max(k, 1), dtype=torch.float32, device=table.device)
+    elif stats.dtype != torch.float32 or stats.numel() != 2 * k or not stats.is_contiguous():
+        raise _lib.KernelError("fedavg_dp_exchange: stats must be contiguous fp32 [2 * sources]")
+    if ws is None:
+        ws = _ws(max(query("sm_fedavg_dp_exchange_workspace_bytes", k, int(num_chunks)), 0), table.device)
+    src = (ctypes.c_int32 * max(1, k))(*[int(i) for i in src_models])
+    dst = (ctypes.c_int32 * max(1, len(dst_models)))(*[int(i) for i in dst_models])
+    wts = (ctypes.c_float * max(1, k))(*[float(w) for w in weights])
+    call("sm_fedavg_dp_exchange", k, ctypes.cast(src, ctypes.c_void_p), ctypes.cast(wts, ctypes.c_void_p),
+         int(global_model), len(dst_models), ctypes.cast(dst, ctypes.c_void_p), ptr(table), table.numel(),
+         ptr(seg_clip), float(clip_norm), float(noise_std), int(seed) & ((1 << 64) - 1), ptr(stats), ptr(ws),
+         ws.numel(), stream())
+    return stats
+
+
 # ------------------------------------------------------------------ clip input pipeline
 def frames_normalize(frames, mean, std, bgr_swap=True, valid=None, out=None):
     """uint8 [B,T,H,W,3] decoded frames -> fp32 [B,3,T,H,W] normalised clip

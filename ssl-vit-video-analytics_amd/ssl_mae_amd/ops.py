@@ -1308,6 +1308,7 @@ def fedavg_counters_max(bufs):
 
 
 FEDAVG_MAX_CLIENTS = _K.FEDAVG_MAX_CLIENTS
+FEDAVG_CHUNK_ELEMS = _K.FEDAVG_CHUNK_ELEMS
 fedavg_exchange_table = _K.fedavg_exchange_table     # host-side table build and upload, no launch
 
 
@@ -1339,6 +1340,30 @@ _fedavg_exchange_counters.register_fake(_none)
 def fedavg_exchange_counters(tensors, src_models, dst_models, table):
     torch.ops.ssl_mae.fedavg_exchange_counters(list(tensors), [int(i) for i in src_models],
                                                [int(i) for i in dst_models], table)
+
+
+# `tensors` as for fedavg_exchange; `stats` (norms, then scales) is written by the finalise launch.
+@_op("fedavg_dp_exchange", "(Tensor(a!)[] tensors, int[] src_models, float[] weights, int global_model, "
+                           "int[] dst_models, Tensor table, int num_chunks, Tensor seg_clip, float clip_norm, "
+                           "float noise_std, int seed, Tensor(b!) stats) -> ()", ("tensors", "stats"))
+def _fedavg_dp_exchange(tensors, src_models, weights, global_model, dst_models, table, num_chunks, seg_clip,
+                        clip_norm, noise_std, seed, stats):
+    _K.fedavg_dp_exchange(list(src_models), list(weights), global_model, list(dst_models), table, num_chunks,
+                          seg_clip, clip_norm, noise_std, _u64(seed), stats)
+
+
+_fedavg_dp_exchange.register_fake(_none)
+
+
+def fedavg_dp_exchange(tensors, src_models, weights, global_model, dst_models, table, num_chunks, seg_clip,
+                       clip_norm, noise_std, seed, stats=None):
+    """-> stats, fp32 [2 * sources] on the device: the update norms, then the clip scales."""
+    if stats is None:
+        stats = torch.empty(2 * len(src_models), dtype=torch.float32, device=table.device)
+    torch.ops.ssl_mae.fedavg_dp_exchange(list(tensors), [int(i) for i in src_models], [float(w) for w in weights],
+                                         int(global_model), [int(i) for i in dst_models], table, int(num_chunks),
+                                         seg_clip, float(clip_norm), float(noise_std), _s64(seed), stats)
+    return stats
 
 
 @_op("frames_normalize", "(Tensor frames, float[] mean, float[] std, bool bgr_swap, Tensor? valid) -> Tensor")

@@ -10,7 +10,10 @@ global and client models -> FedAvg rounds -> fed_summary.csv, centralized_summar
 system_privacy_summary.csv, with the reference's columns and 6-decimal rounding.  The round's
 exchange goes through federated.run_fedavg_fused (one broadcast launch and one aggregation launch
 over the models' tensors where they live); `federated.exchange: reference` keeps run_fedavg's
-state_dict path, with bit-identical model states.
+state_dict path, with bit-identical model states.  `federated.dp.enabled: true` turns the
+aggregation into DP-FedAvg (clipped client updates, Gaussian noise on the aggregate; federated.
+FedCohort.aggregate_dp / dp_aggregate_reference) and adds fed_dp_summary.csv with the round's
+clipping statistics and the accountant's cumulative epsilon ESTIMATE (federated.dp_epsilon).
 
 `make_class_shard_splits` / `read_split` / `write_split` are src/datasets/federated_split.py
 (same random.Random(seed) call order: the same seed writes the same files), `client_update` is
@@ -28,7 +31,7 @@ from pathlib import Path
 import torch
 
 from .driver import SyntheticClips, build_classifier, evaluate, merge_config, split_file_loader, start, train_pass
-from .federated import bytes_to_mb, run_fedavg, run_fedavg_fused
+from .federated import bytes_to_mb, dp_epsilon, run_fedavg, run_fedavg_fused
 from .utils import load_config, log_line
 from .utils import write_csv as _write_csv
 
@@ -37,6 +40,7 @@ FED_COLUMNS = ("round", "val_top1", "val_top5", "avg_local_loss", "clients", "mo
                "comm_mb_total")
 CENTRALIZED_COLUMNS = ("epoch", "train_loss", "val_top1", "val_top5")
 SYSTEM_COLUMNS = ("raw_upload_mb_est", "fed_comm_total_mb", "reduction_ratio")
+DP_COLUMNS = ("round", "clients", "dp_clipped", "dp_norm_mean", "dp_norm_max", "dp_noise_std", "epsilon_est", "delta")
 EXCHANGES = {"fused": run_fedavg_fused, "reference": run_fedavg}
 
 DEFAULTS = {
@@ -46,7 +50,9 @@ DEFAULTS = {
     "federated": {"num_clients": 4, "rounds": 3, "local_epochs": 1, "client_fraction": 1.0, "batch_size": 8,
                   "lr": 3e-4, "weight_decay": 0.01, "exchange": "fused",
                   "non_iid": {"enabled": True, "strategy": "class_shard", "shards_per_client": 6,
-                              "min_samples_per_client": 200}},
+                              "min_samples_per_client": 200},
+                  # DP-FedAvg; seed None: runtime.seed
+                  "dp": {"enabled": False, "clip_norm": 1.0, "noise_multiplier": 0.0, "delta": 1e-5, "seed": None}},
     # None: the federated value (epochs: rounds * local_epochs, the same training budget)
     "centralized": {"enabled": True, "epochs": None, "batch_size": None, "lr": None, "weight_decay": None},
     "system_privacy": {"estimate_raw_upload": True, "raw_dtype_bytes": 1},
@@ -73,6 +79,10 @@ def resolve_config(cfg, save_dir=None, exchange=None):
             or int(fed["batch_size"]) < 1 or int(fed["non_iid"]["shards_per_client"]) < 1:
         raise ValueError("[ERROR] federated: num_clients, batch_size, shards_per_client >= 1; rounds, "
                          "local_epochs >= 0")
+    dp = fed["dp"]
+    if not float(dp["clip_norm"]) > 0.0 or not float(dp["noise_multiplier"]) >= 0.0 \
+            or not 0.0 < float(dp["delta"]) < 1.0:
+        raise ValueError("[ERROR] federated.dp: clip_norm > 0, noise_multiplier >= 0, 0 < delta < 1")
     return out
 
 
@@ -225,6 +235,22 @@ def fed_summary_rows(records):
     return rows, comm_total
 
 
+def dp_summary_rows(records, dp, num_clients):
+    """The rows of fed_dp_summary.csv: the round's clipping statistics and the accountant's
+    estimate of the epsilon spent up to and including that round, at sample rate clients /
+    num_clients (federated.dp_epsilon states what the estimate assumes)."""
+    rows = []
+    for i, r in enumerate(records, 1):
+        eps = dp_epsilon(float(dp["noise_multiplier"]), min(1.0, int(r["clients"]) / max(1, int(num_clients))), i,
+                         float(dp["delta"]))
+        rows.append({"round": r["round"], "clients": int(r["clients"]), "dp_clipped": int(r["dp_clipped"]),
+                     "dp_norm_mean": round(float(r["dp_norm_mean"]), 6),
+                     "dp_norm_max": round(float(r["dp_norm_max"]), 6),
+                     "dp_noise_std": round(float(r["dp_noise_std"]), 6), "epsilon_est": round(eps, 6),
+                     "delta": float(dp["delta"])})
+    return rows
+
+
 def system_privacy_row(raw_upload_mb, fed_comm_mb):
     """run_federated.py:356-360."""
     has_raw = raw_upload_mb is not None
@@ -303,15 +329,26 @@ def main(argv=None):
 
             client_loaders.append({"loader": loader, "update_fn": update_fn})
 
+        dp = fed["dp"]
+        dp_args = {}
+        if bool(dp["enabled"]):        # off: the call below is exactly the plain one
+            dp_args["dp"] = {"clip_norm": float(dp["clip_norm"]), "noise_multiplier": float(dp["noise_multiplier"]),
+                             "seed": seed if dp["seed"] is None else int(dp["seed"])}
+            log(f"[INFO] DP-FedAvg: clip_norm={dp_args['dp']['clip_norm']} "
+                f"noise_multiplier={dp_args['dp']['noise_multiplier']} delta={float(dp['delta'])}")
         records = EXCHANGES[fed["exchange"]](
             global_model, client_models, client_loaders, client_sizes, lambda m: evaluate_topk(m, val_loader, device),
             device, rounds=int(fed["rounds"]), client_fraction=float(fed["client_fraction"]),
-            amp=bool(cfg["runtime"]["amp"]), log_f=log_f)
+            amp=bool(cfg["runtime"]["amp"]), log_f=log_f, **dp_args)
 
         rows, comm_total = fed_summary_rows(records)
         fed_csv = out_dir / "fed_summary.csv"
         _write_csv(fed_csv, FED_COLUMNS, rows)
         log(f"[INFO] Saved federated summary: {fed_csv}")
+        if dp_args:
+            dp_csv = out_dir / "fed_dp_summary.csv"
+            _write_csv(dp_csv, DP_COLUMNS, dp_summary_rows(records, dp, num_clients))
+            log(f"[INFO] Saved DP summary (epsilon_est is an estimate): {dp_csv}")
         sys_row = system_privacy_row(estimate_raw_upload_mb(cfg, train_split), comm_total)
         sys_csv = out_dir / "system_privacy_summary.csv"
         _write_csv(sys_csv, SYSTEM_COLUMNS, [sys_row])
