@@ -3,6 +3,7 @@
 python scripts/kbench.py attn [--drop 0.1] [--iters 5]   # decoder (d=64) + encoder (d=32) attention
 python scripts/kbench.py gemm                              # the main GEMM shapes
 python scripts/kbench.py dynamic --batch 64               # motion scores, dense eval vs streaming early-exit
+python scripts/kbench.py norm                              # LayerNorm, GELU / dropout passes, column sums
 Prints per-kernel-group average ms and TFLOP/s measured with HIP events.
 """
 import argparse
@@ -358,6 +359,55 @@ def mbconv(args):
                                     args.iters), 5)
 
 
+def norm(args):
+    """LayerNorm, the elementwise passes and the column sums (csrc/norm.hip) at the token tensors
+    of the bench step: the decoder's fp32 stream (C = 384, dropout --drop) and the bf16 streams
+    of encoder stages 1-3 (C = 192, 384, 576; DropPath row scale per frame), each with its MLP's
+    hidden width for the GELU passes.  The BatchNorm kernels are timed by `mbconv` and `stem`."""
+    B, dev, bf = args.batch, "cuda", torch.bfloat16
+    stages = [  # (name, rows, rows per DropPath group, C, MLP hidden, stream dtype, dropout p)
+        ("dec", B * 6272, 6272, 384, 1536, torch.float32, args.drop),
+        ("s1", B * 8 * 3136, 3136, 192, 768, bf, 0.0), ("s2", B * 8 * 784, 784, 384, 1536, bf, 0.0),
+        ("s3", B * 8 * 196, 196, 576, 2304, bf, 0.0)]
+
+    def rep(name, fn, *tensors):   # tensors: everything the op reads or writes once
+        ms = timeit(fn, args.iters)
+        gb = sum(t.numel() * t.element_size() for t in tensors) / 1e9
+        print(f"{name:30s} {ms:8.3f} ms  {gb / ms:6.2f} TB/s ({gb:.2f} GB)", flush=True)
+
+    for name, M, L, C, Hd, xd, p in stages:
+        if args.only and args.only not in name:
+            continue
+        x = (torch.randn(M, C, device=dev) * 2 + 0.5).to(xd)
+        res = torch.randn(M, C, device=dev).to(xd)
+        dy = torch.randn(M, C, device=dev).to(bf)
+        g, b = torch.rand(C, device=dev) + 0.5, torch.randn(C, device=dev) * 0.1
+        dg, db = torch.zeros(C, device=dev), torch.zeros(C, device=dev)
+        y, mu, rs = K.layernorm(x, g, b, out_dtype=bf)
+        row_scale = None if name == "dec" else K.droppath_scale(M // L, 0.1, 11, dev)
+        tag = f"{name} [{M}][{C}]"
+        print(f"{tag}: stream {str(xd).split('.')[-1]}, p = {p}, DropPath scale {'on' if row_scale is not None else 'off'}",
+              flush=True)
+        rep(f"{name} C={C} layernorm fwd", lambda: K.layernorm(x, g, b, out_dtype=bf), x, y)
+        rep(f"{name} C={C} layernorm bwd", lambda: K.layernorm_bwd(dy, x, mu, rs, g, dg, db, dres=res), dy, x, res, x)
+        if C in (192, 384):
+            rep(f"{name} C={C} layernorm bwd+branch",
+                lambda: K.layernorm_bwd_branch(dy, x, mu, rs, g, dg, db, dres=res, drop_p=p, seed=7,
+                                               row_scale=row_scale, rows_per_group=L), dy, x, res, x, dy)
+        rep(f"{name} C={C} dropout_bwd", lambda: K.dropout_bwd(dy, p, 7, row_scale, L), dy, dy)
+        if xd == torch.float32:
+            rep(f"{name} C={C} cast_dropout_bwd", lambda: K.cast_dropout_bwd(res, p, 7, row_scale, L), res, dy)
+        rep(f"{name} C={C} colsum", lambda: K.colsum(dy, dg), dy)
+        del x, res, y
+        pre = torch.randn(M, Hd, device=dev).to(bf)
+        d = torch.randn(M, Hd, device=dev).to(bf)
+        rep(f"{name} H={Hd} gelu_fwd", lambda: K.gelu_fwd(pre, p, 7), pre, pre)
+        rep(f"{name} H={Hd} gelu_bwd", lambda: K.gelu_bwd(pre, d, p, 7), pre, d, d)
+        rep(f"{name} H={Hd} colsum", lambda: K.colsum(d, torch.zeros(Hd, device=dev)), d)
+        del pre, d, dy
+        torch.cuda.empty_cache()
+
+
 def bn0fold(args):
     """The expand conv's gradients of a stage-0 MBConv (96 -> 384 at 112^2) behind the depthwise
     backward's first pass: da1 stored + plain GEMMs against BN0's dx map folded into the GEMMs
@@ -478,7 +528,7 @@ def dynamic(args):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["attn", "gemm", "gemmk", "mbconv", "dw", "dwx", "dwse", "stem", "gemmw",
-                                     "bnstats", "dxgelu", "bn0fold", "dynamic"])
+                                     "bnstats", "dxgelu", "bn0fold", "dynamic", "norm"])
     ap.add_argument("--batch", type=int, default=256, help="clips (dynamic: 64 is the reported shape)")
     ap.add_argument("--frames", type=int, default=16, help="dynamic: frames per clip")
     ap.add_argument("--drop", type=float, default=0.1)
@@ -491,4 +541,4 @@ if __name__ == "__main__":
     from ssl_mae_amd.build import build
     build()
     {"attn": attn, "gemm": gemm, "gemmk": gemmk, "mbconv": mbconv, "dw": dw, "dwx": dwx, "dwse": dwse, "stem": stem, "gemmw": gemmw,
-     "bnstats": bnstats, "dxgelu": dxgelu, "bn0fold": bn0fold, "dynamic": dynamic}[a.what](a)
+     "bnstats": bnstats, "dxgelu": dxgelu, "bn0fold": bn0fold, "dynamic": dynamic, "norm": norm}[a.what](a)

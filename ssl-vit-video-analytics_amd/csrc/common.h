@@ -342,5 +342,32 @@ static inline void colred(const float* part, int nb, int ncols, double* outd, fl
                      accumulate);
 }
 
+// BatchNorm backward: sums [2][C] (fp64: sum g, sum g xhat) -> dgamma (+=), dbeta (+=) and
+// the two per-channel coefficients coef [2][C] = mean(g), mean(g xhat) of the dx pass
+static __global__ void bn_bwd_finalize_kernel(const double* sums, int64_t M, int C, float* dw, float* db,
+                                              float* coef) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const double a = sums[c], b = sums[C + c];
+  if (dw) dw[c] += (float)b;
+  if (db) db[c] += (float)a;
+  coef[c] = (float)(a / (double)M);
+  coef[C + c] = (float)(b / (double)M);
+}
+
 #define SM_CHECK_LAUNCH() \
   do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return (int)e__; } while (0)
+
+// Run the statement(s) with T (T1, T2) = float for SM_F32 and __bf16 otherwise
+#define DISPATCH1(DT, ...)                                       \
+  do {                                                         \
+    if ((DT) == SM_F32) { typedef float T; __VA_ARGS__; }      \
+    else { typedef __bf16 T; __VA_ARGS__; }                    \
+  } while (0)
+#define DISPATCH2(DT1, DT2, ...)                                                           \
+  do {                                                                                   \
+    if ((DT1) == SM_F32 && (DT2) == SM_F32) { typedef float T1; typedef float T2; __VA_ARGS__; }     \
+    else if ((DT1) == SM_F32 && (DT2) == SM_BF16) { typedef float T1; typedef __bf16 T2; __VA_ARGS__; } \
+    else if ((DT1) == SM_BF16 && (DT2) == SM_F32) { typedef __bf16 T1; typedef float T2; __VA_ARGS__; } \
+    else { typedef __bf16 T1; typedef __bf16 T2; __VA_ARGS__; }                          \
+  } while (0)

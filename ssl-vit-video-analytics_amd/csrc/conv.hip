@@ -1784,17 +1784,6 @@ __global__ __launch_bounds__(256) void se_bn_combine_kernel(const float* part2, 
   }
 }
 
-// sums [2][C] (fp64) -> dgamma (+=), dbeta (+=), coef [2][C] = mean(du), mean(du xhat)
-__global__ void se_bn_finalize_kernel(const double* sums, int64_t M, int C, float* dw, float* db, float* coef) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const double a = sums[c], b = sums[C + c];
-  if (dw) dw[c] += (float)b;
-  if (db) db[c] += (float)a;
-  coef[c] = (float)(a / (double)M);
-  coef[C + c] = (float)(b / (double)M);
-}
-
 // da2 = w rstd (du - mean(du) - xhat mean(du xhat)),  du = (dh3 s + dpool/HW) GELU'(u),
 // expanded per (frame, channel) into da2 = GELU'(u) (dh3 A + B) + c0 - c1 x with
 // A = w rstd s, B = w rstd dpool/HW, c1 = w rstd^2 mean(du xhat), c0 = w rstd (mean rstd
@@ -1842,12 +1831,6 @@ __global__ __launch_bounds__(256) void se_bn_dx_kernel(const T* dy, const T* x, 
 }
 
 }  // namespace
-
-#define DISPATCH1(DT, ...)                                       \
-  do {                                                         \
-    if ((DT) == SM_F32) { typedef float T; __VA_ARGS__; }      \
-    else { typedef __bf16 T; __VA_ARGS__; }                    \
-  } while (0)
 
 // conv_out divides by the stride: only 1 and 2 exist, checked once per entry point
 static bool bad_stride(int s) { return s != 1 && s != 2; }
@@ -2135,7 +2118,7 @@ static int dwconv_bn_bwd(int stride, int F, int H, int W, int C, const void* dy,
   colred(part_w, F, C * 9, nullptr, dw, 1, st);
   colred(part_bn, F, 2 * C, sums, nullptr, 0, st);
   const int64_t M = (int64_t)F * H * W;
-  hipLaunchKernelGGL(se_bn_finalize_kernel, dim3((C + 127) / 128), dim3(128), 0, st, sums, M, C, dgamma, dbeta,
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 127) / 128), dim3(128), 0, st, sums, M, C, dgamma, dbeta,
                      coef);
   if (coef_out) {
     SM_CHECK_LAUNCH();
@@ -2287,7 +2270,7 @@ extern "C" int sm_se_bn_bwd(int dtype, const void* dy, const void* x, const floa
                      dpool);
   hipLaunchKernelGGL(se_bn_combine_kernel, dim3(F), dim3(256), 0, st, part2, ns, HW, C, s, dpool, comb);
   colred(comb, F, 2 * C, sums, nullptr, 0, st);
-  hipLaunchKernelGGL(se_bn_finalize_kernel, dim3((C + 127) / 128), dim3(128), 0, st, sums, (int64_t)F * HW, C, dw,
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 127) / 128), dim3(128), 0, st, sums, (int64_t)F * HW, C, dw,
                      db, coef);
   DISPATCH1(dtype, hipLaunchKernelGGL(se_bn_dx_kernel<T>, dim3(ns, F), dim3(256), 0, st, (const T*)dy, (const T*)x,
                                       act, s, dpool, coef, (T*)dx, HW, C));

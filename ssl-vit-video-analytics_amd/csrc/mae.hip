@@ -508,12 +508,6 @@ inline int ew_blocks(int64_t n) {
 
 }  // namespace
 
-#define DISPATCH1(DT, ...)                                       \
-  do {                                                         \
-    if ((DT) == SM_F32) { typedef float T; __VA_ARGS__; }      \
-    else { typedef __bf16 T; __VA_ARGS__; }                    \
-  } while (0)
-
 extern "C" int sm_tube_mask(const float* noise, int B, int T, int L, int n_mask, uint8_t* mask, int32_t* idx,
                             hipStream_t st) {
   if (B <= 0 || T <= 0 || L <= 0) return 0;

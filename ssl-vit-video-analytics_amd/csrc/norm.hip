@@ -15,6 +15,29 @@
 namespace {
 
 // ============================================================ LayerNorm
+// Per-chunk arithmetic (4 columns of one row; gamma / beta at g[c0 + j]) shared by the two
+// lane layouts: 64 lanes per row with a `ci < nch` guard (any C), and 16 / 32 lanes per row
+// with DPP sums (C = 192, 384).  The layouts keep their own loads / stores (`nt` hints), row
+// reductions and mean forms (`/ C` against `* (1.f / C)`: these round differently), and the
+// two one-line loops (squared deviations, dx) whose helper forms cost the 64-lane kernels
+// registers (profiles/norm_cleanup_isa_and_ab.txt).
+SM_DEV void ln_out4(const float (&v)[4], float mu, float rs, const float* g, const float* b, int c0, float (&o)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = (v[j] - mu) * rs * g[c0 + j] + b[c0 + j];
+}
+// xh = x_hat, gy = gamma dy, their row-sum terms s1 / s2 and the dgamma / dbeta accumulation
+SM_DEV void ln_bwd_acc4(const float (&xv)[4], const float (&dv)[4], float mu, float rs, const float* g, int c0,
+                        float (&xh)[4], float (&gy)[4], float& s1, float& s2, float (&ag)[4], float (&ab)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    xh[j] = (xv[j] - mu) * rs;
+    gy[j] = dv[j] * g[c0 + j];
+    s1 += gy[j];
+    s2 += gy[j] * xh[j];
+    ag[j] += dv[j] * xh[j];
+    ab[j] += dv[j];
+  }
+}
 template <typename TI, typename TO>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const TI* x, const float* g, const float* b, TO* y,
                                                      float* mean, float* rstd, int64_t M, int C, float eps) {
@@ -51,11 +74,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const TI* x, const float* g
     const int ci = l + 64 * i;
     if (ci < nch) {
       float o[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = ci * 4 + j;
-        o[j] = (v[i][j] - mu) * rs * g[c] + b[c];
-      }
+      ln_out4(v[i], mu, rs, g, b, ci * 4, o);
       store4(yr + ci * 4, o);
     }
   }
@@ -72,11 +91,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const TD* dy, const TI* x, 
   __shared__ float red_g[4][1024], red_b[4][1024];
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   const int nch = C / 4;
-  float ag[MAXV][4], ab[MAXV][4];
-#pragma unroll
-  for (int i = 0; i < MAXV; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { ag[i][j] = 0.f; ab[i][j] = 0.f; }
+  float ag[MAXV][4] = {}, ab[MAXV][4] = {};
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
   for (int rr = w; rr < rows_per_block; rr += 4) {
     const int64_t row = r0 + rr;
@@ -91,16 +106,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const TD* dy, const TI* x, 
         float xv[4], dv[4];
         load4(x + row * C + ci * 4, xv);
         load4(dy + row * C + ci * 4, dv);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int c = ci * 4 + j;
-          xh[i][j] = (xv[j] - mu) * rs;
-          gg[i][j] = dv[j] * g[c];
-          s1 += gg[i][j];
-          s2 += gg[i][j] * xh[i][j];
-          ag[i][j] += dv[j] * xh[i][j];
-          ab[i][j] += dv[j];
-        }
+        ln_bwd_acc4(xv, dv, mu, rs, g, ci * 4, xh[i], gg[i], s1, s2, ag[i], ab[i]);
       }
     }
     s1 = wave_sum(s1) / C;
@@ -136,8 +142,6 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const TD* dy, const TI* x, 
     part_b[(int64_t)blockIdx.x * C + c] = red_b[0][c] + red_b[1][c] + red_b[2][c] + red_b[3][c];
   }
 }
-
-
 
 // ---------------------------------------------- LayerNorm, 16 lanes per row (C = 192, 384)
 // Four rows per wave (one per 16-lane DPP row), 16 rows per block in flight, a block
@@ -191,12 +195,28 @@ __global__ __launch_bounds__(256) void ln_fwd16_kernel(const TI* x, const float*
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       float o[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = (v[u][j] - mu) * rs * gg[u][j] + bb[u][j];
+      ln_out4(v[u], mu, rs, gg[u], bb[u], 0, o);
       store4(yr + 64 * u, o);   // (read back by the next GEMM: a normal store measured faster for bf16 x)
     }
     if (gl == 0) { mean[row] = mu; rstd[row] = rs; }
   }
+}
+
+// Dropout multipliers (keep ? scale : 0) of 4 consecutive columns, col % 4 == 0: one hash
+SM_DEV void drop_mult4(uint32_t rowbase, uint32_t col, uint32_t thr, float ks, float* m) {
+  const uint32_t h = drop_hash(rowbase, col);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) m[j] = ((h >> (8 * j)) & 0xFFu) >= thr ? ks : 0.f;
+}
+// 8 consecutive elements of one row (ncols % 8 == 0, checked by every entry point that
+// passes drop_p > 0)
+SM_DEV void drop_mult8(int64_t e, int ncols, float drop_p, uint64_t seed, float* m) {
+  const float ks = drop_scale(drop_p);
+  const int64_t row = e / ncols;
+  const uint32_t c0 = (uint32_t)(e - row * ncols);
+  const uint32_t rb = drop_rowbase(seed32(seed), (uint64_t)row), thr = drop_thr(drop_p);
+  drop_mult4(rb, c0, thr, ks, m);
+  drop_mult4(rb, c0 + 4, thr, ks, m + 4);
 }
 
 // dx (+ dres) and per-block partial dgamma / dbeta (part_g/part_b [block][C]).
@@ -231,13 +251,9 @@ __global__ __launch_bounds__(256) void ln_bwd16_kernel(const TD* dy, const TI* x
   static_assert(U * 4 * G == C, "C must split over the row's lanes");
   __shared__ float red[2][4][C];
   const int gl = threadIdx.x & (G - 1), grp = threadIdx.x / G, w = threadIdx.x >> 6;
-  float gw[U][4], ag[U][4], ab[U][4];
+  float gw[U][4], ag[U][4] = {}, ab[U][4] = {};
 #pragma unroll
-  for (int u = 0; u < U; ++u) {
-    load4(g + 4 * G * u + 4 * gl, gw[u]);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { ag[u][j] = 0.f; ab[u][j] = 0.f; }
-  }
+  for (int u = 0; u < U; ++u) load4(g + 4 * G * u + 4 * gl, gw[u]);
   auto row_sum = [](float v) {
     v = sum16(v);
     if constexpr (G == 32) v += __shfl_xor(v, 16, 64);
@@ -255,15 +271,7 @@ __global__ __launch_bounds__(256) void ln_bwd16_kernel(const TD* dy, const TI* x
       float xv[4], dv[4];
       load4_nt(x + e0 + 4 * G * u, xv);
       load4_nt(dy + e0 + 4 * G * u, dv);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        xh[u][j] = (xv[j] - mu) * rs;
-        gy[u][j] = dv[j] * gw[u][j];
-        s1 += gy[u][j];
-        s2 += gy[u][j] * xh[u][j];
-        ag[u][j] += dv[j] * xh[u][j];
-        ab[u][j] += dv[j];
-      }
+      ln_bwd_acc4(xv, dv, mu, rs, gw[u], 0, xh[u], gy[u], s1, s2, ag[u], ab[u]);
     }
     s1 = row_sum(s1) * (1.f / C);
     s2 = row_sum(s2) * (1.f / C);
@@ -281,16 +289,14 @@ __global__ __launch_bounds__(256) void ln_bwd16_kernel(const TD* dy, const TI* x
       store4_nt(dx + e0 + 4 * G * u, o);
       if (br.bo) {
         const float rsv = br.rs ? br.rs[row / br.rpg] : 1.f;
-        const float ks = br.p > 0.f ? drop_scale(br.p) : 1.f;
-        const uint32_t hsh = br.p > 0.f ? drop_hash(drop_rowbase(seed32(br.seed), (uint64_t)row),
-                                                     (uint32_t)(4 * G * u + 4 * gl)) : 0u;
-        const uint32_t thr = drop_thr(br.p);
-        float b4[4];
+        float m[4] = {1.f, 1.f, 1.f, 1.f}, b4[4];
+        if (br.p > 0.f)
+          drop_mult4(drop_rowbase(seed32(br.seed), (uint64_t)row), (uint32_t)(4 * G * u + 4 * gl), drop_thr(br.p),
+                     drop_scale(br.p), m);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const float d = (float)(__bf16)to_f<TI>(from_f<TI>(o[j]));   // the stored dx, cast to bf16
-          const float mj = br.p > 0.f ? (((hsh >> (8 * j)) & 0xFFu) >= thr ? ks : 0.f) : 1.f;
-          b4[j] = d * (rsv * mj);
+          b4[j] = d * (rsv * m[j]);
         }
         store4_nt(br.bo + e0 + 4 * G * u, b4);
       }
@@ -328,26 +334,51 @@ __global__ __launch_bounds__(256) void ln_bwd16_kernel(const TD* dy, const TI* x
 }
 
 // ============================================================ BatchNorm (train)
-// Thread layout shared by the column-reduction kernels: thread t owns the 4-wide
-// channel chunk t % (C/4) and rows r = t / (C/4) (mod rows-per-pass).
-struct ColMap {
+// Channel-owning thread layout of the [M][C] kernels: thread t owns the W-wide channel
+// chunk t % (C/W) for rows t / (C/W) (+ k * rows-per-pass), C / W <= 256.  W = 4: the
+// column-reduction kernels; W = 8: the streaming kernels (per-channel parameters in
+// registers, rows walked with 16-byte loads).
+template <int W>
+struct ColOwner {
   int nch, rpp, chunk, r;
-  SM_DEV ColMap(int C) {
-    nch = C / 4;
+  SM_DEV ColOwner(int C) {
+    nch = C / W;
     rpp = 256 / nch;
     if (rpp < 1) rpp = 1;
     chunk = threadIdx.x % nch;
     r = threadIdx.x / nch;
   }
-  SM_DEV bool active() const { return r < rpp && chunk < nch; }
+  SM_DEV bool active() const { return r < rpp; }
 };
+
+// Block epilogue of the column-reduction kernels: every thread's NQ x 4 sums -> LDS ->
+// per-column sum over the rpp row groups (ascending) -> part[block][q][C]
+template <int NQ>
+SM_DEV void col_partials(const ColOwner<4>& cm, int C, const float (&v)[NQ][4], float (*red)[256 * 4], float* part) {
+#pragma unroll
+  for (int q = 0; q < NQ; ++q)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) red[q][threadIdx.x * 4 + j] = v[q][j];
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) {
+    const int ch = c / 4, j = c % 4;
+    float a[NQ] = {};
+    for (int rr = 0; rr < cm.rpp; ++rr) {
+      const int t = rr * cm.nch + ch;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) a[q] += red[q][t * 4 + j];
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) part[((int64_t)blockIdx.x * NQ + q) * C + c] = a[q];
+  }
+}
 
 template <typename T>
 __global__ __launch_bounds__(256) void bn_stats_kernel(const T* x, int64_t M, int C, int64_t ld, int rows_per_block,
                                                        float* part /*[nb][2][C]*/) {
   __shared__ float red[2][256 * 4];
-  ColMap cm(C);
-  float s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
+  ColOwner<4> cm(C);
+  float sq[2][4] = {};   // sum, sum of squares of x - shift
   float shift[4];
   load4(x + cm.chunk * 4, shift);   // per-channel shift = first row (robust variance)
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
@@ -357,23 +388,10 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const T* x, int64_t M, in
       float v[4];
       load4(x + row * ld + cm.chunk * 4, v);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { const float d = v[j] - shift[j]; s[j] += d; q[j] += d * d; }
+      for (int j = 0; j < 4; ++j) { const float d = v[j] - shift[j]; sq[0][j] += d; sq[1][j] += d * d; }
     }
   }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { red[0][threadIdx.x * 4 + j] = s[j]; red[1][threadIdx.x * 4 + j] = q[j]; }
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += 256) {
-    const int ch = c / 4, j = c % 4;
-    float a = 0.f, b = 0.f;
-    for (int rr = 0; rr < cm.rpp; ++rr) {
-      const int t = rr * cm.nch + ch;
-      a += red[0][t * 4 + j];
-      b += red[1][t * 4 + j];
-    }
-    part[((int64_t)blockIdx.x * 2 + 0) * C + c] = a;
-    part[((int64_t)blockIdx.x * 2 + 1) * C + c] = b;
-  }
+  col_partials<2>(cm, C, sq, red, part);
 }
 
 template <typename T>
@@ -403,27 +421,12 @@ __global__ void bn_finalize_kernel(const double* sums /*[2][C]*/, const T* x, in
   }
 }
 
-// Channel-owning layout for [M][C] streaming kernels: thread t owns the 8-channel
-// chunk t % (C/8) for rows t / (C/8) (+ k * rows-per-pass); per-channel parameters
-// live in registers and rows are walked with 16-byte loads.
-struct Col8 {
-  int nch, rpp, chunk, r;
-  SM_DEV Col8(int C) {
-    nch = C / 8;
-    rpp = 256 / nch;
-    if (rpp < 1) rpp = 1;
-    chunk = threadIdx.x % nch;
-    r = threadIdx.x / nch;
-  }
-  SM_DEV bool active() const { return r < rpp; }
-};
-
 template <typename TI, typename TO>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const TI* x, const float* mean, const float* rstd,
                                                        const float* w, const float* b, TO* y, int64_t M, int C,
                                                        int rows_per_block, int gelu, const TO* R,
                                                        const float* row_scale, int64_t rpg, ChanAffine raff) {
-  Col8 cm(C);
+  ColOwner<8> cm(C);
   if (!cm.active()) return;
   float sc[8], sh[8];
 #pragma unroll
@@ -465,7 +468,22 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const TI* x, const float*
   }
 }
 
-// per-channel sums of g and g*x_hat where g = dy (* gelu'(bn(x)) when gelu)
+// BatchNorm backward of a packed pair of channels (gelu_phi_pair_t): xh = x_hat and
+// g = dy * row_scale (* gelu'(bn(x)) when gelu).  The reduce and the dx kernel must agree.
+struct BnBwdPair {
+  f32x2 xh, g;
+};
+SM_DEV f32x2 pair_at(const float* a, int j) { return f32x2{a[j], a[j + 1]}; }
+SM_DEV BnBwdPair bn_bwd_pair(int j, const float* xv, const float* dv, const float* mu, const float* rs,
+                             const float* w, const float* b, float rsc, int gelu) {
+  BnBwdPair p;
+  p.xh = (pair_at(xv, j) - pair_at(mu, j)) * pair_at(rs, j);
+  p.g = pair_at(dv, j) * rsc;
+  if (gelu) p.g *= gelu_grad2(vfma(p.xh, pair_at(w, j), pair_at(b, j)));
+  return p;
+}
+
+// per-channel sums of g and g*x_hat
 template <typename TI, typename TD>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const TD* dy, const TI* x, const float* mean,
                                                             const float* rstd, const float* w, const float* b,
@@ -473,8 +491,8 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const TD* dy, const 
                                                             int gelu, const float* row_scale, int64_t rpg,
                                                             float* part) {
   __shared__ float red[2][256 * 4];
-  ColMap cm(C);
-  float sg[4] = {0, 0, 0, 0}, sgx[4] = {0, 0, 0, 0};
+  ColOwner<4> cm(C);
+  float sg[2][4] = {};   // sum g, sum g x_hat
   float mu[4], rs[4], ww[4], bb[4];
   if (cm.active()) {
 #pragma unroll
@@ -490,44 +508,17 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const TD* dy, const 
       load4_nt(dy + row * ld + cm.chunk * 4, dv);
       const float rsc = row_scale ? row_scale[row / rpg] : 1.f;
 #pragma unroll
-      for (int j = 0; j < 4; j += 2) {   // packed pairs (gelu_phi_pair_t)
-        const f32x2 xh = (f32x2{xv[j], xv[j + 1]} - f32x2{mu[j], mu[j + 1]}) * f32x2{rs[j], rs[j + 1]};
-        f32x2 gg = f32x2{dv[j], dv[j + 1]} * rsc;
-        if (gelu) gg *= gelu_grad2(vfma(xh, f32x2{ww[j], ww[j + 1]}, f32x2{bb[j], bb[j + 1]}));
+      for (int j = 0; j < 4; j += 2) {
+        const BnBwdPair p = bn_bwd_pair(j, xv, dv, mu, rs, ww, bb, rsc, gelu);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-          sg[j + i] += gg[i];
-          sgx[j + i] += gg[i] * xh[i];
+          sg[0][j + i] += p.g[i];
+          sg[1][j + i] += p.g[i] * p.xh[i];
         }
       }
     }
   }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { red[0][threadIdx.x * 4 + j] = sg[j]; red[1][threadIdx.x * 4 + j] = sgx[j]; }
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += 256) {
-    const int ch = c / 4, j = c % 4;
-    float a = 0.f, bsum = 0.f;
-    for (int rr = 0; rr < cm.rpp; ++rr) {
-      const int t = rr * cm.nch + ch;
-      a += red[0][t * 4 + j];
-      bsum += red[1][t * 4 + j];
-    }
-    part[((int64_t)blockIdx.x * 2 + 0) * C + c] = a;
-    part[((int64_t)blockIdx.x * 2 + 1) * C + c] = bsum;
-  }
-}
-
-// sums -> dgamma (+=), dbeta (+=), and the two per-channel coefficients for dx
-__global__ void bn_bwd_finalize_kernel(const double* sums /*[2][C]*/, int64_t M, int C, float* dw, float* db,
-                                       float* coef /*[2][C]: mean(g), mean(g*xhat)*/) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const double a = sums[c], b = sums[C + c];
-  if (dw) dw[c] += (float)b;
-  if (db) db[c] += (float)a;
-  coef[c] = (float)(a / (double)M);
-  coef[C + c] = (float)(b / (double)M);
+  col_partials<2>(cm, C, sg, red, part);
 }
 
 template <typename TI, typename TD, typename TX>
@@ -536,7 +527,7 @@ __global__ __launch_bounds__(256) void bn_bwd_dx_kernel(const TD* dy, const TI* 
                                                         const float* coef, TX* dx, int64_t M, int C, int64_t ld,
                                                         int rows_per_block, int gelu, const float* row_scale,
                                                         int64_t rpg) {
-  Col8 cm(C);
+  ColOwner<8> cm(C);
   if (!cm.active()) return;
   float mu[8], rs[8], ww[8], bb[8], k0[8], k1[8];
 #pragma unroll
@@ -553,12 +544,10 @@ __global__ __launch_bounds__(256) void bn_bwd_dx_kernel(const TD* dy, const TI* 
     float o[8];
     const float rsc = row_scale ? row_scale[row / rpg] : 1.f;
 #pragma unroll
-    for (int j = 0; j < 8; j += 2) {   // packed pairs (gelu_phi_pair_t)
-      const f32x2 xh = (f32x2{xv[j], xv[j + 1]} - f32x2{mu[j], mu[j + 1]}) * f32x2{rs[j], rs[j + 1]};
-      f32x2 gg = f32x2{dv[j], dv[j + 1]} * rsc;
-      if (gelu) gg *= gelu_grad2(vfma(xh, f32x2{ww[j], ww[j + 1]}, f32x2{bb[j], bb[j + 1]}));
+    for (int j = 0; j < 8; j += 2) {
+      const BnBwdPair p = bn_bwd_pair(j, xv, dv, mu, rs, ww, bb, rsc, gelu);
 #pragma unroll
-      for (int i = 0; i < 2; ++i) o[j + i] = ww[j + i] * rs[j + i] * (gg[i] - k0[j + i] - xh[i] * k1[j + i]);
+      for (int i = 0; i < 2; ++i) o[j + i] = ww[j + i] * rs[j + i] * (p.g[i] - k0[j + i] - p.xh[i] * k1[j + i]);
     }
     store8(dx + e, o);   // (read next by the branch GEMM: normal store, +1 % with nt)
   };
@@ -582,26 +571,25 @@ __global__ __launch_bounds__(256) void bn_bwd_dx_kernel(const TD* dy, const TI* 
   }
 }
 
-// ============================================================ elementwise
-// 8 consecutive elements of one row (ncols % 8 == 0): dropout multipliers
-SM_DEV void drop_mult8(int64_t e, int ncols, float drop_p, uint64_t seed, float* m) {
-  const float ks = drop_scale(drop_p);
-  const int64_t row = e / ncols;
-  const uint32_t c0 = (uint32_t)(e - row * ncols);
-  const uint32_t rb = drop_rowbase(seed32(seed), (uint64_t)row), thr = drop_thr(drop_p);
-#pragma unroll
-  for (int j4 = 0; j4 < 8; j4 += 4) {
-    const uint32_t h = drop_hash(rb, c0 + j4);    // c0 % 8 == 0
-#pragma unroll
-    for (int j = 0; j < 4; ++j) m[j4 + j] = ((h >> (8 * j)) & 0xFFu) >= thr ? ks : 0.f;
-  }
+// eval-mode BatchNorm (running statistics): mean = running_mean, rstd = 1/sqrt(var + eps),
+// in the form every BN consumer (bn_apply, the folded ChanAffine loads) takes
+__global__ void bn_eval_params_kernel(const float* run_mean, const float* run_var, int C, float eps, float* mean,
+                                      float* rstd) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  mean[c] = run_mean[c];
+  rstd[c] = 1.0f / sqrtf(run_var[c] + eps);
 }
+
+// ============================================================ elementwise
+// grid-stride loop over the 8-element groups i of a flat tensor
+#define FOR_EACH8(i, total8) \
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (total8); i += (int64_t)gridDim.x * blockDim.x)
 
 template <typename T, typename TG>
 __global__ void gelu_bwd_kernel(const T* pre, const TG* dy, TG* dx, int64_t total8, int ncols, float drop_p,
                                 uint64_t seed) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total8;
-       i += (int64_t)gridDim.x * blockDim.x) {
+  FOR_EACH8(i, total8) {
     float p[8], d[8], m[8];
     load8(pre + i * 8, p);
     load8(dy + i * 8, d);
@@ -622,8 +610,7 @@ __global__ void gelu_bwd_kernel(const T* pre, const TG* dy, TG* dx, int64_t tota
 template <typename T, typename TO = T>
 __global__ void dropout_bwd_kernel(const T* dy, TO* dx, int64_t total8, int ncols, float drop_p, uint64_t seed,
                                    const float* row_scale, int64_t rpg) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total8;
-       i += (int64_t)gridDim.x * blockDim.x) {
+  FOR_EACH8(i, total8) {
     float d[8], m[8];
     load8(dy + i * 8, d);
     if (sizeof(TO) < sizeof(T)) {
@@ -646,8 +633,7 @@ __global__ void droppath_scale_kernel(int n, float p, uint64_t seed, float* out)
 
 template <typename TA, typename TB, typename TO>
 __global__ void add_kernel(const TA* a, const TB* b, TO* o, int64_t total8) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total8;
-       i += (int64_t)gridDim.x * blockDim.x) {
+  FOR_EACH8(i, total8) {
     float x[8], y[8];
     load8(a + i * 8, x);
     load8(b + i * 8, y);
@@ -659,8 +645,7 @@ __global__ void add_kernel(const TA* a, const TB* b, TO* o, int64_t total8) {
 
 template <typename TA, typename TO>
 __global__ void cast_kernel(const TA* a, TO* o, int64_t total8) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total8;
-       i += (int64_t)gridDim.x * blockDim.x) {
+  FOR_EACH8(i, total8) {
     float x[8];
     load8(a + i * 8, x);
     store8(o + i * 8, x);
@@ -669,8 +654,7 @@ __global__ void cast_kernel(const TA* a, TO* o, int64_t total8) {
 
 template <typename T>
 __global__ void gelu_fwd_kernel(const T* x, T* y, int64_t total8, int ncols, float drop_p, uint64_t seed) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total8;
-       i += (int64_t)gridDim.x * blockDim.x) {
+  FOR_EACH8(i, total8) {
     float v[8], m[8];
     load8(x + i * 8, v);
     if (drop_p > 0.f) drop_mult8(i * 8, ncols, drop_p, seed, m);
@@ -688,9 +672,9 @@ __global__ void gelu_fwd_kernel(const T* x, T* y, int64_t total8, int ncols, flo
 template <typename T>
 __global__ __launch_bounds__(256) void colsum_part_kernel(const T* x, int64_t ld, int64_t M, int C,
                                                           int rows_per_block, float* part) {
-  __shared__ float red[256 * 4];
-  ColMap cm(C);
-  float s[4] = {0, 0, 0, 0};
+  __shared__ float red[1][256 * 4];
+  ColOwner<4> cm(C);
+  float s[1][4] = {};
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
   const int64_t r1 = min(M, r0 + rows_per_block);
   if (cm.active())
@@ -698,45 +682,74 @@ __global__ __launch_bounds__(256) void colsum_part_kernel(const T* x, int64_t ld
       float v[4];
       load4(x + row * ld + cm.chunk * 4, v);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) s[j] += v[j];
+      for (int j = 0; j < 4; ++j) s[0][j] += v[j];
     }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) red[threadIdx.x * 4 + j] = s[j];
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += 256) {
-    const int ch = c / 4, j = c % 4;
-    float a = 0.f;
-    for (int rr = 0; rr < cm.rpp; ++rr) a += red[(rr * cm.nch + ch) * 4 + j];
-    part[(int64_t)blockIdx.x * C + c] = a;
-  }
+  col_partials<1>(cm, C, s, red, part);
 }
 
+// ============================================================ launch geometry
 inline int ew_blocks(int64_t n8) {
   int64_t b = (n8 + 255) / 256;
   if (b > 8192) b = 8192;
   return b < 1 ? 1 : (int)b;
 }
-// rows per block for the channel-owning streaming kernels (~4096 blocks)
-inline int stream_rows_per_block(int64_t M) {
-  int64_t r = (M + 4095) / 4096;
-  if (r < 16) r = 16;
-  return (int)r;
+// A block walks a contiguous run of `rpb` rows: about `blocks` blocks, at least `min_rows`
+// rows each, rpb a multiple of `quantum`.
+struct RowSplit {
+  int rpb, nb;
+};
+inline RowSplit row_split(int64_t M, int64_t blocks, int64_t min_rows, int64_t quantum = 1) {
+  int64_t r = ((M + blocks - 1) / blocks + quantum - 1) / quantum * quantum;
+  if (r < min_rows) r = min_rows;
+  return RowSplit{(int)r, (int)((M + r - 1) / r)};
 }
-inline int red_rows_per_block(int64_t M, int C) {
-  // aim for ~2048 blocks, at least 64 rows each
-  int64_t r = (M + 2047) / 2048;
-  if (r < 64) r = 64;
-  return (int)r;
+inline RowSplit red_split(int64_t M) { return row_split(M, 2048, 64); }      // column reductions
+inline RowSplit stream_split(int64_t M) { return row_split(M, 4096, 16); }   // channel-owning streaming kernels
+inline RowSplit ln_fwd16_split(int64_t M) { return row_split(M, 4096, 16, 16); }
+
+// f(c0, cs) for the channel slices [c0, c0 + cs) of width <= `width` over the same [M][C] rows
+template <typename F>
+inline void for_channel_slices(int C, int width, F f) {
+  for (int c0 = 0; c0 < C; c0 += width) f(c0, min(width, C - c0));
+}
+inline int esize(int dtype) { return dtype == SM_BF16 ? 2 : 4; }
+
+// ColOwner<4> covers 256 chunks of 4 channels: BatchNorm over more channels (stage-4 MBConv,
+// 1536) runs in equal column slices, a multiple of 8 wide
+const int BN_MAX_SLICE = 1024;
+inline int bn_slice_width(int C) {
+  const int nsl = (C + BN_MAX_SLICE - 1) / BN_MAX_SLICE;
+  return nsl == 1 ? C : (C / nsl + 7) / 8 * 8;
+}
+
+// BatchNorm workspace: part [nb][2][C] fp32 | sums [2][C] fp64, 8-byte aligned | coef [2][C]
+// fp32 (backward only).  Sizes first: the pointers are formed after the size check.
+struct BnWorkspace {
+  int64_t part_bytes;
+  int C;
+  int64_t stats_bytes, bwd_bytes;   // what sm_bn_stats / sm_bn_bwd need
+  int64_t reported_bytes;           // what sm_bn_workspace_bytes reports (more slack)
+  float* part(void* ws) const { return (float*)ws; }
+  double* sums(void* ws) const { return (double*)(((uintptr_t)ws + part_bytes + 7) & ~(uintptr_t)7); }
+  float* coef(void* ws) const { return (float*)(sums(ws) + 2 * C); }
+};
+inline BnWorkspace bn_workspace(int nb, int C) {
+  const int64_t part_bytes = (int64_t)nb * 2 * C * 4, sums_bytes = (int64_t)2 * C * 8, coef_bytes = (int64_t)2 * C * 4;
+  BnWorkspace w{part_bytes, C};
+  w.stats_bytes = part_bytes + sums_bytes + 8;
+  w.bwd_bytes = w.stats_bytes + coef_bytes;
+  w.reported_bytes = part_bytes + sums_bytes + coef_bytes + 64;
+  return w;
 }
 
 }  // namespace
 
-#define DISPATCH2(DT1, DT2, ...)                                                           \
-  do {                                                                                   \
-    if ((DT1) == SM_F32 && (DT2) == SM_F32) { typedef float T1; typedef float T2; __VA_ARGS__; }     \
-    else if ((DT1) == SM_F32 && (DT2) == SM_BF16) { typedef float T1; typedef __bf16 T2; __VA_ARGS__; } \
-    else if ((DT1) == SM_BF16 && (DT2) == SM_F32) { typedef __bf16 T1; typedef float T2; __VA_ARGS__; } \
-    else { typedef __bf16 T1; typedef __bf16 T2; __VA_ARGS__; }                          \
+// C = 384 and 192 have LayerNorm kernels compiled for them (FIXED, with LN_C); GENERIC serves every other C
+#define LN_DISPATCH_C(C, FIXED, GENERIC)                         \
+  do {                                                           \
+    if ((C) == 384) { constexpr int LN_C = 384; FIXED; }         \
+    else if ((C) == 192) { constexpr int LN_C = 192; FIXED; }    \
+    else { GENERIC; }                                            \
   } while (0)
 
 extern "C" int sm_layernorm_fwd(int x_dtype, int y_dtype, int64_t M, int C, const void* x, const float* gamma,
@@ -744,38 +757,46 @@ extern "C" int sm_layernorm_fwd(int x_dtype, int y_dtype, int64_t M, int C, cons
                                 hipStream_t st) {
   if (M <= 0) return 0;
   if (C % 4 || C > 1024) return -2;
-  if (C == 384 || C == 192) {
-    int64_t rpb = ((M + 4095) / 4096 + 15) / 16 * 16;   // ~4096 blocks, 16-row multiples
-    if (rpb < 16) rpb = 16;
-    const int nb = (int)((M + rpb - 1) / rpb);
-    if (C == 384)
-      DISPATCH2(x_dtype, y_dtype,
-                hipLaunchKernelGGL((ln_fwd16_kernel<T1, T2, 384>), dim3(nb), dim3(256), 0, st, (const T1*)x, gamma,
-                                   beta, (T2*)y, mean, rstd, M, eps, rpb));
-    else
-      DISPATCH2(x_dtype, y_dtype,
-                hipLaunchKernelGGL((ln_fwd16_kernel<T1, T2, 192>), dim3(nb), dim3(256), 0, st, (const T1*)x, gamma,
-                                   beta, (T2*)y, mean, rstd, M, eps, rpb));
-    SM_CHECK_LAUNCH();
-    return 0;
-  }
-  const int blocks = (int)((M + 3) / 4);
-  DISPATCH2(x_dtype, y_dtype,
-            hipLaunchKernelGGL((ln_fwd_kernel<T1, T2>), dim3(blocks), dim3(256), 0, st, (const T1*)x, gamma,
-                               beta, (T2*)y, mean, rstd, M, C, eps));
+  const RowSplit rs = ln_fwd16_split(M);
+  LN_DISPATCH_C(C,
+                DISPATCH2(x_dtype, y_dtype,
+                          hipLaunchKernelGGL((ln_fwd16_kernel<T1, T2, LN_C>), dim3(rs.nb), dim3(256), 0, st,
+                                             (const T1*)x, gamma, beta, (T2*)y, mean, rstd, M, eps, (int64_t)rs.rpb)),
+                DISPATCH2(x_dtype, y_dtype,
+                          hipLaunchKernelGGL((ln_fwd_kernel<T1, T2>), dim3((int)((M + 3) / 4)), dim3(256), 0, st,
+                                             (const T1*)x, gamma, beta, (T2*)y, mean, rstd, M, C, eps)));
   SM_CHECK_LAUNCH();
   return 0;
 }
 
-extern "C" int64_t sm_layernorm_bwd_workspace_bytes(int64_t M, int C) {
-  const int64_t rpb = red_rows_per_block(M, C);
-  const int64_t nb = (M + rpb - 1) / rpb;
-  return nb * C * 4 * 2;
-}
+extern "C" int64_t sm_layernorm_bwd_workspace_bytes(int64_t M, int C) { return (int64_t)red_split(M).nb * C * 4 * 2; }
 
 static int layernorm_bwd(int x_dtype, int dy_dtype, int dx_dtype, int64_t M, int C, const void* dy, const void* x,
                          const float* mean, const float* rstd, const float* gamma, void* dx, const void* dres,
-                         float* dgamma, float* dbeta, void* ws, int64_t ws_bytes, LnBranch br, hipStream_t st);
+                         float* dgamma, float* dbeta, void* ws, int64_t ws_bytes, LnBranch br, hipStream_t st) {
+  if (M <= 0) return 0;
+  if (C % 4 || C > 1024) return -2;
+  const RowSplit rd = red_split(M);
+  const int rpb = rd.rpb, nb = rd.nb;
+  if (ws_bytes < (int64_t)nb * C * 8) return -4;
+  float* pg = (float*)ws;
+  float* pb = pg + (int64_t)nb * C;
+  if (x_dtype != dx_dtype) return -3;   // dx has the dtype of the LN input stream
+  LN_DISPATCH_C(C,
+                DISPATCH2(x_dtype, dy_dtype,
+                          hipLaunchKernelGGL((ln_bwd16_kernel<T1, T2, LN_C>), dim3(nb), dim3(256), 0, st,
+                                             (const T2*)dy, (const T1*)x, mean, rstd, gamma, (T1*)dx, pg, pb, M,
+                                             (int64_t)rpb, (const T1*)dres, br)),
+                DISPATCH2(x_dtype, dy_dtype,
+                          hipLaunchKernelGGL((ln_bwd_kernel<T1, T2, T1>), dim3(nb), dim3(256), 0, st, (const T2*)dy,
+                                             (const T1*)x, mean, rstd, gamma, (T1*)dx, pg, pb, M, C, rpb,
+                                             (const T1*)dres)));
+  SM_CHECK_LAUNCH();
+  colred(pg, nb, C, nullptr, dgamma, 1, st);
+  colred(pb, nb, C, nullptr, dbeta, 1, st);
+  SM_CHECK_LAUNCH();
+  return 0;
+}
 
 // dx (+)= LN backward; dgamma/dbeta (+)= (accumulated into the fp32 grad sinks)
 extern "C" int sm_layernorm_bwd(int x_dtype, int dy_dtype, int dx_dtype, int64_t M, int C, const void* dy,
@@ -799,97 +820,35 @@ extern "C" int sm_layernorm_bwd_branch(int x_dtype, int dy_dtype, int dx_dtype, 
                        ws_bytes, LnBranch{(__bf16*)dxb, drop_p, seed, row_scale, rows_per_group}, st);
 }
 
-static int layernorm_bwd(int x_dtype, int dy_dtype, int dx_dtype, int64_t M, int C, const void* dy, const void* x,
-                         const float* mean, const float* rstd, const float* gamma, void* dx, const void* dres,
-                         float* dgamma, float* dbeta, void* ws, int64_t ws_bytes, LnBranch br, hipStream_t st) {
-  if (M <= 0) return 0;
-  if (C % 4 || C > 1024) return -2;
-  const int rpb = red_rows_per_block(M, C);
-  const int nb = (int)((M + rpb - 1) / rpb);
-  if (ws_bytes < (int64_t)nb * C * 8) return -4;
-  float* pg = (float*)ws;
-  float* pb = pg + (int64_t)nb * C;
-  if (x_dtype != dx_dtype) return -3;   // dx has the dtype of the LN input stream
-  if (C == 384)
-    DISPATCH2(x_dtype, dy_dtype,
-              hipLaunchKernelGGL((ln_bwd16_kernel<T1, T2, 384>), dim3(nb), dim3(256), 0, st, (const T2*)dy,
-                                 (const T1*)x, mean, rstd, gamma, (T1*)dx, pg, pb, M, (int64_t)rpb, (const T1*)dres, br));
-  else if (C == 192)
-    DISPATCH2(x_dtype, dy_dtype,
-              hipLaunchKernelGGL((ln_bwd16_kernel<T1, T2, 192>), dim3(nb), dim3(256), 0, st, (const T2*)dy,
-                                 (const T1*)x, mean, rstd, gamma, (T1*)dx, pg, pb, M, (int64_t)rpb, (const T1*)dres, br));
-  else
-    DISPATCH2(x_dtype, dy_dtype,
-              hipLaunchKernelGGL((ln_bwd_kernel<T1, T2, T1>), dim3(nb), dim3(256), 0, st, (const T2*)dy,
-                                 (const T1*)x, mean, rstd, gamma, (T1*)dx, pg, pb, M, C, rpb, (const T1*)dres));
-  SM_CHECK_LAUNCH();
-  colred(pg, nb, C, nullptr, dgamma, 1, st);
-  colred(pb, nb, C, nullptr, dbeta, 1, st);
-  SM_CHECK_LAUNCH();
-  return 0;
-}
-
 extern "C" int64_t sm_bn_workspace_bytes(int64_t M, int C) {
-  const int64_t rpb = red_rows_per_block(M, C);
-  const int64_t nb = (M + rpb - 1) / rpb;
-  return nb * 2 * C * 4 + 2 * C * 8 + 2 * C * 4 + 64;
+  return bn_workspace(red_split(M).nb, C).reported_bytes;
 }
 
-// batch statistics -> mean/rstd (+ running-stat update `updates` times).  Channels
-// above 1024 (stage-4 MBConv, 1536) are processed in column slices of the same
-// [M][C] rows (row stride C).
-static const int BN_MAX_SLICE = 1024;
-
-static int bn_stats_slice(int x_dtype, int64_t M, int C, int64_t ld, const void* x, float* mean, float* rstd,
-                          float* run_mean, float* run_var, int64_t* nbt, float momentum, float eps, int updates,
-                          float* part, double* sums, hipStream_t st) {
-  const int rpb = red_rows_per_block(M, C);
-  const int nb = (int)((M + rpb - 1) / rpb);
-  if (x_dtype == SM_BF16) {
-    hipLaunchKernelGGL(bn_stats_kernel<__bf16>, dim3(nb), dim3(256), 0, st, (const __bf16*)x, M, C, ld, rpb, part);
-    colred(part, nb, 2 * C, sums, nullptr, 0, st);
-    hipLaunchKernelGGL(bn_finalize_kernel<__bf16>, dim3((C + 127) / 128), dim3(128), 0, st, sums,
-                       (const __bf16*)x, M, C, eps, momentum, mean, rstd, run_mean, run_var, updates, nbt);
-  } else {
-    hipLaunchKernelGGL(bn_stats_kernel<float>, dim3(nb), dim3(256), 0, st, (const float*)x, M, C, ld, rpb, part);
-    colred(part, nb, 2 * C, sums, nullptr, 0, st);
-    hipLaunchKernelGGL(bn_finalize_kernel<float>, dim3((C + 127) / 128), dim3(128), 0, st, sums,
-                       (const float*)x, M, C, eps, momentum, mean, rstd, run_mean, run_var, updates, nbt);
-  }
-  return 0;
-}
-
+// batch statistics -> mean/rstd (+ running-stat update `updates` times)
 extern "C" int sm_bn_stats(int x_dtype, int64_t M, int C, const void* x, float* mean, float* rstd,
                            float* run_mean, float* run_var, int64_t* num_batches_tracked, float momentum, float eps,
                            int updates, void* ws, int64_t ws_bytes, hipStream_t st) {
   if (M <= 0) return -2;
   if (C % 4 || C > 4 * BN_MAX_SLICE || (C > BN_MAX_SLICE && C % 8)) return -2;
-  const int rpb = red_rows_per_block(M, C);
-  const int nb = (int)((M + rpb - 1) / rpb);
-  if (ws_bytes < (int64_t)nb * 2 * C * 4 + 2 * C * 8 + 8) return -4;
-  float* part = (float*)ws;
-  double* sums = (double*)(((uintptr_t)(part + (int64_t)nb * 2 * C) + 7) & ~(uintptr_t)7);
-  const int nsl = (C + BN_MAX_SLICE - 1) / BN_MAX_SLICE;
-  const int w = nsl == 1 ? C : (C / nsl + 7) / 8 * 8;
-  const size_t es = x_dtype == SM_BF16 ? 2 : 4;
-  for (int c0 = 0; c0 < C; c0 += w) {
-    const int cs = min(w, C - c0);
-    bn_stats_slice(x_dtype, M, cs, C, (const char*)x + c0 * es, mean + c0, rstd + c0,
-                   run_mean ? run_mean + c0 : nullptr, run_var ? run_var + c0 : nullptr,
-                   c0 == 0 ? num_batches_tracked : nullptr, momentum, eps, updates, part, sums, st);
-  }
+  const RowSplit rd = red_split(M);
+  const int rpb = rd.rpb, nb = rd.nb;
+  const BnWorkspace w = bn_workspace(nb, C);
+  if (ws_bytes < w.stats_bytes) return -4;
+  float* part = w.part(ws);
+  double* sums = w.sums(ws);
+  for_channel_slices(C, bn_slice_width(C), [&](int c0, int cs) {
+    const void* xo = (const char*)x + c0 * esize(x_dtype);
+    DISPATCH1(x_dtype,
+              hipLaunchKernelGGL(bn_stats_kernel<T>, dim3(nb), dim3(256), 0, st, (const T*)xo, M, cs, (int64_t)C, rpb,
+                                 part);
+              colred(part, nb, 2 * cs, sums, nullptr, 0, st);
+              hipLaunchKernelGGL(bn_finalize_kernel<T>, dim3((cs + 127) / 128), dim3(128), 0, st, sums,
+                                 (const T*)xo, M, cs, eps, momentum, mean + c0, rstd + c0,
+                                 run_mean ? run_mean + c0 : nullptr, run_var ? run_var + c0 : nullptr, updates,
+                                 c0 == 0 ? num_batches_tracked : nullptr));
+  });
   SM_CHECK_LAUNCH();
   return 0;
-}
-
-// eval-mode BatchNorm (running statistics): mean = running_mean, rstd = 1/sqrt(var + eps),
-// in the form every BN consumer (bn_apply, the folded ChanAffine loads) takes
-__global__ void bn_eval_params_kernel(const float* run_mean, const float* run_var, int C, float eps, float* mean,
-                                      float* rstd) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  mean[c] = run_mean[c];
-  rstd[c] = 1.0f / sqrtf(run_var[c] + eps);
 }
 
 extern "C" int sm_bn_eval_params(const float* run_mean, const float* run_var, int C, float eps, float* mean,
@@ -921,19 +880,26 @@ extern "C" int sm_bn_stats_from_partials(const float* part, int64_t nrows, int C
   return 0;
 }
 
+static int bn_apply(int x_dtype, int y_dtype, int64_t M, int C, const void* x, const float* mean, const float* rstd,
+                    const float* w, const float* b, void* y, int gelu, const void* R, ChanAffine raff,
+                    const float* row_scale, int64_t rows_per_group, hipStream_t st) {
+  const RowSplit ss = stream_split(M);
+  const int rpb = ss.rpb, nb = ss.nb;
+  DISPATCH2(x_dtype, y_dtype,
+            hipLaunchKernelGGL((bn_apply_kernel<T1, T2>), dim3(nb), dim3(256), 0, st, (const T1*)x,
+                               mean, rstd, w, b, (T2*)y, M, C, rpb, gelu, (const T2*)R, row_scale,
+                               rows_per_group > 0 ? rows_per_group : 1, raff));
+  SM_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int sm_bn_apply(int x_dtype, int y_dtype, int64_t M, int C, const void* x, const float* mean,
                            const float* rstd, const float* w, const float* b, void* y, int gelu,
                            const void* R, const float* row_scale, int64_t rows_per_group, hipStream_t st) {
   if (M <= 0) return 0;
   if (C % 8 || C / 8 > 256) return -2;
-  const int rpb = stream_rows_per_block(M);
-  const int nb = (int)((M + rpb - 1) / rpb);
-  DISPATCH2(x_dtype, y_dtype,
-            hipLaunchKernelGGL((bn_apply_kernel<T1, T2>), dim3(nb), dim3(256), 0, st, (const T1*)x,
-                               mean, rstd, w, b, (T2*)y, M, C, rpb, gelu, (const T2*)R, row_scale,
-                               rows_per_group > 0 ? rows_per_group : 1, ChanAffine{}));
-  SM_CHECK_LAUNCH();
-  return 0;
+  return bn_apply(x_dtype, y_dtype, M, C, x, mean, rstd, w, b, y, gelu, R, ChanAffine{}, row_scale, rows_per_group,
+                  st);
 }
 
 // sm_bn_apply with the residual R stored before its own BatchNorm (the stem's conv2 output
@@ -949,15 +915,8 @@ extern "C" int sm_bn_apply_res_bn(int x_dtype, int y_dtype, int64_t M, int C, co
   if (C % 8 || C / 8 > 256 || R == nullptr || r_mean == nullptr || r_rstd == nullptr || r_w == nullptr ||
       r_b == nullptr)
     return -2;
-  const int rpb = stream_rows_per_block(M);
-  const int nb = (int)((M + rpb - 1) / rpb);
-  const ChanAffine raff{r_mean, r_rstd, r_w, r_b, 0};
-  DISPATCH2(x_dtype, y_dtype,
-            hipLaunchKernelGGL((bn_apply_kernel<T1, T2>), dim3(nb), dim3(256), 0, st, (const T1*)x,
-                               mean, rstd, w, b, (T2*)y, M, C, rpb, gelu, (const T2*)R, row_scale,
-                               rows_per_group > 0 ? rows_per_group : 1, raff));
-  SM_CHECK_LAUNCH();
-  return 0;
+  return bn_apply(x_dtype, y_dtype, M, C, x, mean, rstd, w, b, y, gelu, R, ChanAffine{r_mean, r_rstd, r_w, r_b, 0},
+                  row_scale, rows_per_group, st);
 }
 
 extern "C" int sm_bn_bwd(int x_dtype, int g_dtype, int64_t M, int C, const void* dy, const void* x,
@@ -967,22 +926,17 @@ extern "C" int sm_bn_bwd(int x_dtype, int g_dtype, int64_t M, int C, const void*
   const int64_t rpg = rows_per_group > 0 ? rows_per_group : 1;
   if (M <= 0) return 0;
   if (C % 8 || C > 4 * BN_MAX_SLICE) return -2;
-  const int rpb = red_rows_per_block(M, C);
-  const int nb = (int)((M + rpb - 1) / rpb);
-  if (ws_bytes < (int64_t)nb * 2 * C * 4 + 2 * C * 8 + 2 * C * 4 + 8) return -4;
-  float* part = (float*)ws;
-  double* sums = (double*)(((uintptr_t)(part + (int64_t)nb * 2 * C) + 7) & ~(uintptr_t)7);
-  float* coef = (float*)(sums + 2 * C);
-  const int srpb = stream_rows_per_block(M);
-  const int snb = (int)((M + srpb - 1) / srpb);
-  const int nsl = (C + BN_MAX_SLICE - 1) / BN_MAX_SLICE;
-  const int wd = (C / nsl + 7) / 8 * 8;
-  const size_t xs = x_dtype == SM_BF16 ? 2 : 4, gs = g_dtype == SM_BF16 ? 2 : 4;
-  for (int c0 = 0; c0 < C; c0 += wd) {   // channel slices of <= 1024 over the same rows
-    const int cs = min(wd, C - c0);
-    const void* xo = (const char*)x + c0 * xs;
-    const void* dyo = (const char*)dy + c0 * gs;
-    void* dxo = (char*)dx + c0 * gs;
+  const RowSplit rd = red_split(M), ss = stream_split(M);
+  const int rpb = rd.rpb, nb = rd.nb, srpb = ss.rpb, snb = ss.nb;
+  const BnWorkspace k = bn_workspace(nb, C);
+  if (ws_bytes < k.bwd_bytes) return -4;
+  float* part = k.part(ws);
+  double* sums = k.sums(ws);
+  float* coef = k.coef(ws);
+  for_channel_slices(C, bn_slice_width(C), [&](int c0, int cs) {
+    const void* xo = (const char*)x + c0 * esize(x_dtype);
+    const void* dyo = (const char*)dy + c0 * esize(g_dtype);
+    void* dxo = (char*)dx + c0 * esize(g_dtype);
     DISPATCH2(x_dtype, g_dtype,
               hipLaunchKernelGGL((bn_bwd_reduce_kernel<T1, T2>), dim3(nb), dim3(256), 0, st, (const T2*)dyo,
                                  (const T1*)xo, mean + c0, rstd + c0, w + c0, b + c0, M, cs, (int64_t)C, rpb, gelu,
@@ -992,17 +946,21 @@ extern "C" int sm_bn_bwd(int x_dtype, int g_dtype, int64_t M, int C, const void*
                        db + c0, coef);
     DISPATCH2(x_dtype, g_dtype,
               hipLaunchKernelGGL((bn_bwd_dx_kernel<T1, T2, T2>), dim3(snb), dim3(256), 0, st,
-                                 (const T2*)dyo, (const T1*)xo, mean + c0, rstd + c0, w + c0, b + c0, coef, (T2*)dxo,
-                                 M, cs, (int64_t)C, srpb, gelu, row_scale, rpg));
-  }
+                                 (const T2*)dyo, (const T1*)xo, mean + c0, rstd + c0, w + c0, b + c0, coef,
+                                 (T2*)dxo, M, cs, (int64_t)C, srpb, gelu, row_scale, rpg));
+  });
   SM_CHECK_LAUNCH();
   return 0;
 }
 
+// the 8-wide elementwise kernels take whole groups; a dropout mask (drop_p > 0) also needs a
+// group to lie in one row (drop_mult8)
+static bool bad_ew_shape(int64_t n, int ncols, float drop_p) { return n % 8 || (drop_p > 0.f && ncols % 8); }
+
 extern "C" int sm_gelu_bwd(int pre_dtype, int g_dtype, int64_t n, int ncols, const void* pre, const void* dy,
                            void* dx, float drop_p, uint64_t seed, hipStream_t st) {
   if (n <= 0) return 0;
-  if (n % 8) return -2;
+  if (bad_ew_shape(n, ncols, drop_p)) return -2;
   DISPATCH2(pre_dtype, g_dtype,
             hipLaunchKernelGGL((gelu_bwd_kernel<T1, T2>), dim3(ew_blocks(n / 8)), dim3(256), 0, st,
                                (const T1*)pre, (const T2*)dy, (T2*)dx, n / 8, ncols, drop_p, seed));
@@ -1031,32 +989,23 @@ extern "C" int sm_cast(int a_dtype, int o_dtype, int64_t n, const void* a, void*
   return 0;
 }
 
-extern "C" int64_t sm_colsum_workspace_bytes(int64_t M, int C) {
-  const int64_t rpb = red_rows_per_block(M, C);
-  return ((M + rpb - 1) / rpb) * C * 4;
-}
+extern "C" int64_t sm_colsum_workspace_bytes(int64_t M, int C) { return (int64_t)red_split(M).nb * C * 4; }
 
 // out[c] (+)= sum_m x[m][c]   (bias gradients)
 extern "C" int sm_colsum(int dtype, int64_t M, int C, const void* x, float* out, int accumulate, void* ws,
                          int64_t ws_bytes, hipStream_t st) {
   if (M <= 0) return 0;
   if (C % 4) return -2;
-  const int rpb = red_rows_per_block(M, C);
-  const int nb = (int)((M + rpb - 1) / rpb);
+  const RowSplit rd = red_split(M);
+  const int rpb = rd.rpb, nb = rd.nb;
   if (ws_bytes < (int64_t)nb * C * 4) return -4;
-  const int esz = dtype == SM_BF16 ? 2 : 4;
-  for (int c0 = 0; c0 < C; c0 += 1024) {       // 1024-column slices (ColMap covers <= 256 chunks of 4)
-    const int cs = C - c0 < 1024 ? C - c0 : 1024;
-    const char* xs = (const char*)x + (int64_t)c0 * esz;
-    float* part = (float*)ws;
-    if (dtype == SM_BF16)
-      hipLaunchKernelGGL(colsum_part_kernel<__bf16>, dim3(nb), dim3(256), 0, st, (const __bf16*)xs, (int64_t)C, M,
-                         cs, rpb, part);
-    else
-      hipLaunchKernelGGL(colsum_part_kernel<float>, dim3(nb), dim3(256), 0, st, (const float*)xs, (int64_t)C, M, cs,
-                         rpb, part);
+  float* part = (float*)ws;
+  for_channel_slices(C, 1024, [&](int c0, int cs) {   // ColOwner<4> covers <= 256 chunks of 4
+    const char* xs = (const char*)x + (int64_t)c0 * esize(dtype);
+    DISPATCH1(dtype, hipLaunchKernelGGL(colsum_part_kernel<T>, dim3(nb), dim3(256), 0, st, (const T*)xs, (int64_t)C, M,
+                                        cs, rpb, part));
     colred(part, nb, cs, nullptr, out + c0, accumulate, st);
-  }
+  });
   SM_CHECK_LAUNCH();
   return 0;
 }
@@ -1064,13 +1013,9 @@ extern "C" int sm_colsum(int dtype, int64_t M, int C, const void* x, float* out,
 extern "C" int sm_gelu_fwd(int dtype, int64_t n, int ncols, const void* x, void* y, float drop_p, uint64_t seed,
                            hipStream_t st) {
   if (n <= 0) return 0;
-  if (n % 8) return -2;
-  if (dtype == SM_BF16)
-    hipLaunchKernelGGL(gelu_fwd_kernel<__bf16>, dim3(ew_blocks(n / 8)), dim3(256), 0, st, (const __bf16*)x,
-                       (__bf16*)y, n / 8, ncols, drop_p, seed);
-  else
-    hipLaunchKernelGGL(gelu_fwd_kernel<float>, dim3(ew_blocks(n / 8)), dim3(256), 0, st, (const float*)x, (float*)y,
-                       n / 8, ncols, drop_p, seed);
+  if (bad_ew_shape(n, ncols, drop_p)) return -2;
+  DISPATCH1(dtype, hipLaunchKernelGGL(gelu_fwd_kernel<T>, dim3(ew_blocks(n / 8)), dim3(256), 0, st, (const T*)x, (T*)y,
+                                      n / 8, ncols, drop_p, seed));
   SM_CHECK_LAUNCH();
   return 0;
 }
@@ -1080,12 +1025,8 @@ extern "C" int sm_dropout_bwd(int dtype, int64_t n, int ncols, const void* dy, v
   if (n <= 0) return 0;
   if (n % 8 || ncols % 8) return -2;
   const int64_t rpg = rows_per_group > 0 ? rows_per_group : 1;
-  if (dtype == SM_BF16)
-    hipLaunchKernelGGL(dropout_bwd_kernel<__bf16>, dim3(ew_blocks(n / 8)), dim3(256), 0, st, (const __bf16*)dy,
-                       (__bf16*)dx, n / 8, ncols, drop_p, seed, row_scale, rpg);
-  else
-    hipLaunchKernelGGL(dropout_bwd_kernel<float>, dim3(ew_blocks(n / 8)), dim3(256), 0, st, (const float*)dy,
-                       (float*)dx, n / 8, ncols, drop_p, seed, row_scale, rpg);
+  DISPATCH1(dtype, hipLaunchKernelGGL(dropout_bwd_kernel<T>, dim3(ew_blocks(n / 8)), dim3(256), 0, st, (const T*)dy,
+                                      (T*)dx, n / 8, ncols, drop_p, seed, row_scale, rpg));
   SM_CHECK_LAUNCH();
   return 0;
 }

@@ -127,6 +127,16 @@ def test_colsum():
     assert rel_err(out, x.sum(0) + 1) < 1e-5
 
 
+def test_colsum_two_slices_ragged_rows():
+    """C = 1536: two 1024-column slices; M = 130: three row blocks of 64, 64 and 2 rows; added
+    to a non-zero `out`."""
+    x = rnd(130, 1536, seed=14)
+    init = rnd(1536, seed=15)
+    out = init.to(DEV)
+    KK().colsum(x.to(DEV), out, accumulate=True)
+    assert rel_err(out, x.sum(0) + init) < 1e-5
+
+
 # ------------------------------------------------------------------ attention
 def _attn_ref(qkv, N, L, H, D):
     qkv = qkv.float().reshape(N, L, 3, H, D).permute(2, 0, 3, 1, 4)
@@ -307,11 +317,120 @@ def test_attention_argument_checks(dtype):
     assert untouched(o, lse, dqkv) and not ws.any()
 
 
+def test_norm_argument_checks():
+    """The norm.hip entry points refuse a bad call before any launch: -2 for a shape, -3 for the
+    LayerNorm backward's dtype pair, -4 for a workspace one byte short of what the entry point
+    checks, and 0 for an empty tensor; in every case the sentinel-filled outputs stay untouched.
+    The exact workspace size is accepted."""
+    from ssl_mae_amd import _lib
+    q, P = _lib.query, _lib.ptr
+    st = _lib.stream()
+    M, C, SENT = 64, 192, 7.0
+    F32, BF16 = _lib.dt(torch.empty(0)), _lib.dt(torch.empty(0, dtype=torch.bfloat16))
+    n_max = M * 1028
+    a = rnd(n_max, seed=95).to(DEV)                 # inputs: any [M][C <= 1028] tensor
+    b = rnd(n_max, seed=96).to(DEV)
+    v = (rnd(1028, seed=97) * 0.1 + 1).to(DEV)      # per-channel / per-row inputs
+    outs = [torch.full((n_max,), SENT, device=DEV) for _ in range(2)]
+    o1, o2 = outs
+    ob = torch.full((n_max + 8,), SENT, dtype=torch.bfloat16, device=DEV)
+    s1, s2 = [torch.full((1028,), SENT, device=DEV) for _ in range(2)]
+    ws = torch.full((1 << 16,), 7, dtype=torch.uint8, device=DEV)
+    WS = ws.numel()
+
+    def untouched():
+        torch.cuda.synchronize()
+        return all(bool((t == SENT).all()) for t in (o1, o2, ob, s1, s2, ws))
+
+    def ln_fwd(m, c):
+        return q("sm_layernorm_fwd", F32, F32, m, c, P(a), P(v), P(v), P(o1), P(s1), P(s2), 1e-5, st)
+
+    def ln_bwd(m, c, dxd=F32, nbytes=WS):
+        return q("sm_layernorm_bwd", F32, F32, dxd, m, c, P(b), P(a), P(v), P(v), P(v), P(o1), None, P(s1), P(s2),
+                 P(ws), nbytes, st)
+
+    def ln_branch(m, c, dxb):
+        return q("sm_layernorm_bwd_branch", F32, F32, F32, m, c, P(b), P(a), P(v), P(v), P(v), P(o1), None, P(s1),
+                 P(s2), dxb, 0.1, 5, None, 8, P(ws), WS, st)
+
+    def bn_stats(m, c, nbytes=WS):
+        return q("sm_bn_stats", F32, m, c, P(a), P(s1), P(s2), None, None, None, 0.1, 1e-5, 1, P(ws), nbytes, st)
+
+    def bn_apply(m, c):
+        return q("sm_bn_apply", F32, F32, m, c, P(a), P(v), P(v), P(v), P(v), P(o1), 1, None, None, 1, st)
+
+    def bn_bwd(m, c, nbytes=WS):
+        return q("sm_bn_bwd", F32, F32, m, c, P(b), P(a), P(v), P(v), P(v), P(v), 1, None, 1, P(o1), P(s1), P(s2),
+                 P(ws), nbytes, st)
+
+    def gelu_fwd(n, ncols, p=0.0):
+        return q("sm_gelu_fwd", F32, n, ncols, P(a), P(o1), p, 5, st)
+
+    def gelu_bwd(n, ncols, p=0.0):
+        return q("sm_gelu_bwd", F32, F32, n, ncols, P(a), P(b), P(o1), p, 5, st)
+
+    def add(n):
+        return q("sm_add", F32, F32, n, P(a), P(b), P(o1), st)
+
+    def cast(n):
+        return q("sm_cast", F32, BF16, n, P(a), P(ob), st)
+
+    def dropout_bwd(n, ncols):
+        return q("sm_dropout_bwd", F32, n, ncols, P(a), P(o1), 0.1, 5, None, 1, st)
+
+    def cast_dropout_bwd(n, ncols):
+        return q("sm_cast_dropout_bwd", n, ncols, P(a), P(ob), 0.1, 5, None, 1, st)
+
+    def colsum(m, c, nbytes=WS):
+        return q("sm_colsum", F32, m, c, P(a), P(s1), 0, P(ws), nbytes, st)
+
+    # -2: shapes
+    for c in (190, 1028):                                   # C % 4, C > 1024
+        assert ln_fwd(M, c) == -2 and ln_bwd(M, c) == -2
+    assert ln_branch(M, 576, P(ob)) == -2                   # the branch copy exists for C = 192 / 384
+    assert ln_branch(M, C, None) == -2
+    assert ob.data_ptr() % 8 == 0
+    assert ln_branch(M, C, ob.data_ptr() + 2) == -2         # dxb not 8-byte aligned
+    assert bn_apply(M, 196) == -2                           # C % 8
+    assert gelu_fwd(12, 12) == -2 and gelu_bwd(12, 12) == -2 and add(12) == -2 and cast(12) == -2   # n % 8
+    assert dropout_bwd(96, 12) == -2                        # ncols % 8
+    assert gelu_fwd(96, 12, 0.1) == -2 and gelu_bwd(96, 12, 0.1) == -2   # a mask group must lie in one row
+    # -3: dx has the dtype of x
+    assert ln_bwd(M, C, dxd=BF16) == -3
+    # -4: one byte short of the checked size (one row block: nb = 1)
+    nb = (M + 63) // 64
+    need = {"ln": nb * C * 8, "stats": nb * 2 * C * 4 + 2 * C * 8 + 8, "colsum": nb * C * 4}
+    need["bwd"] = need["stats"] + 2 * C * 4
+    assert need["ln"] == q("sm_layernorm_bwd_workspace_bytes", M, C)
+    assert need["colsum"] == q("sm_colsum_workspace_bytes", M, C)
+    assert need["bwd"] + 56 == q("sm_bn_workspace_bytes", M, C)
+    assert ln_bwd(M, C, nbytes=need["ln"] - 1) == -4
+    assert bn_stats(M, C, need["stats"] - 1) == -4
+    assert bn_bwd(M, C, need["bwd"] - 1) == -4
+    assert colsum(M, C, need["colsum"] - 1) == -4
+    # 0: nothing to do (sm_bn_stats has no statistics of zero rows: -2)
+    assert ln_fwd(0, C) == 0 and ln_bwd(0, C) == 0 and ln_branch(0, C, P(ob)) == 0
+    assert bn_stats(0, C) == -2 and bn_apply(0, C) == 0 and bn_bwd(0, C) == 0 and colsum(0, C) == 0
+    assert gelu_fwd(0, C) == 0 and gelu_bwd(0, C) == 0 and add(0) == 0 and cast(0) == 0
+    assert dropout_bwd(0, C) == 0 and cast_dropout_bwd(0, C) == 0
+    assert q("sm_droppath_scale", 0, 0.1, 5, P(s1), st) == 0
+    assert untouched()
+    # the exact size is accepted
+    assert ln_bwd(M, C, nbytes=need["ln"]) == 0
+    assert bn_stats(M, C, need["stats"]) == 0
+    assert bn_bwd(M, C, need["bwd"]) == 0
+    assert colsum(M, C, need["colsum"]) == 0
+    torch.cuda.synchronize()
+    assert not untouched()
+
+
 # ------------------------------------------------------------------ LayerNorm
 @pytest.mark.parametrize("xd,yd", [(torch.float32, torch.float32), (torch.bfloat16, torch.bfloat16),
                                    (torch.float32, torch.bfloat16)])
-@pytest.mark.parametrize("C", [192, 384])
+@pytest.mark.parametrize("C", [192, 384, 576, 100])
 def test_layernorm(xd, yd, C):
+    """C = 192 / 384: the 16- and 32-lane kernels; C = 576 (stage 3, the classifier) and C = 100
+    (25 chunks of 4: a partly filled first pass over the row's 64 lanes): the generic kernels."""
     M = 777
     x = (rnd(M, C, seed=40) * 3 + 1).to(xd)
     g = rnd(C, seed=41) * 0.1 + 1
