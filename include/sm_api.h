@@ -709,6 +709,47 @@ int sm_fedavg_dp_exchange(int num_src, const int32_t* src_models, const float* w
                           const uint8_t* seg_clip, float clip_norm, float noise_std, uint64_t seed, float* stats,
                           void* ws, int64_t ws_bytes, hipStream_t st);
 
+/* ---- Compressed FedAvg round exchange (int8 block quantisation with error feedback: Seide et al.
+ * 2014, Karimireddy et al. 2019; not in the reference) over the fp32 FedAvg exchange table above, in
+ * one launch with no workspace.  src_models, weights (already normalised), global_model and dst_models
+ * as for sm_fedavg_dp_exchange; every source is a client model: a source equal to global_model is -2.
+ * seg_mode (DEVICE, one byte per segment): 1 = quantised, 0 = sm_fedavg_exchange's plain weighted sum
+ * of the sources, bit for bit.
+ * resid (DEVICE, fp32 [num_rows][num_chunks * SM_FEDAVG_CHUNK_ELEMS], 16-byte aligned): the sources'
+ * quantisation residuals, row = model index - 1, element c * SM_FEDAVG_CHUNK_ELEMS + i = element i of
+ * chunk c; read and updated in place for the quantised chunks' elements, nothing else is touched.
+ * A block is SM_FEDAVG_Q8_BLOCK consecutive elements of a chunk.  For every element of a quantised
+ * segment, for every source j in source order, every operation rounded on its own (no fma):
+ *   v    = fadd_rn(fsub_rn(x_j, theta), e_j)
+ *   m    = max over the block of |v| (exact; a NaN in the block makes m NaN; slots past the chunk's
+ *          end count as 0)
+ *   live = m >= 1e-30f and m finite
+ *   s    = live ? fdiv_rn(m, 127) : 0,  inv = live ? fdiv_rn(127, m) : 0
+ *   q    = live ? clamp(rint(fmul_rn(v, inv)), -127, 127) : 0      (round-half-even)
+ *   d    = fmul_rn((float)q, s);  e_j = fsub_rn(v, d)             (a dead block keeps all of v)
+ *   acc  = theta, then acc = fadd_rn(acc, fmul_rn(weights[j], d)) in source order
+ * and acc goes to the element in every dst model.  What a client uploads is (q, s): one byte per
+ * element and one fp32 per block.  The payload is optional -- with codes or scales NULL neither is
+ * written: codes (DEVICE, int8 [num_src][num_chunks][SM_FEDAVG_CHUNK_ELEMS], 4-byte aligned) and
+ * scales (DEVICE, fp32 [num_src][num_chunks][SM_FEDAVG_CHUNK_ELEMS / SM_FEDAVG_Q8_BLOCK]), written in
+ * full: zeros for slots past a chunk's end and for chunks of mode-0 segments.
+ * part (DEVICE, double [num_src][num_chunks][2]) receives, for every chunk, (max |v| of the chunk,
+ * sum of the squares of the chunk's new residual): the squares are fp32, a lane adds its 8 in fp32
+ * in ascending order, everything above a lane is fp64 in a fixed order -- the same bits on every
+ * call; (0, 0) for the chunks of mode-0 segments.  No atomics.
+ * A lane loads its elements from theta and every source before its first store into a model, so
+ * destinations may alias sources and theta; resid, codes, scales and part overlap no model.  A chunk
+ * moves as 16-byte vectors when it is 16-byte aligned in every model of the launch, else element by
+ * element, with the same bits.
+ * Returns -2 as sm_fedavg_exchange does, and for NULL weights / seg_mode / resid / part, global_model
+ * outside [0, P), num_rows < 1, or a source that is global_model or whose row is outside
+ * [0, num_rows); -4 for a misaligned resid, part, codes or scales.  Nothing is written in either case. */
+#define SM_FEDAVG_Q8_BLOCK 256
+int sm_fedavg_q8_exchange(int num_src, const int32_t* src_models, const float* weights, int global_model,
+                          int num_dst, const int32_t* dst_models, const void* table, int64_t table_bytes,
+                          const uint8_t* seg_mode, float* resid, int num_rows, int8_t* codes, float* scales,
+                          double* part, hipStream_t st);
+
 /* ---- clip input pipeline (src/train_ssl_mae.py:137-141 PILToTensor + ConvertImageDtype +
  * Normalize; src/datasets/mae_loader.py:70-77 BGR swap img[[2,1,0]] and [C,T,H,W] stack).
  * frames uint8 [B][T][H][W][3] (decoded RGB) -> out fp32 [B][3][T][H][W],

@@ -23,6 +23,11 @@
   (FedCohort.aggregate_dp, three launches) against the plain aggregate and the eager
   dp_aggregate_reference in the same process, with each launch's time and bandwidth (see `fed_dp`).
 
+* `aux_bench.py fed_q8 [--out profiles/fed_q8.txt]`: the compressed aggregation
+  (FedCohort.aggregate_q8, one launch) with and without the payload against the plain aggregate
+  and the eager q8_aggregate_reference in the same process, with the launch's bandwidth (see
+  `fed_q8`).
+
 Prints one JSON line per kernel; run under rocprofv3 --kernel-trace --stats to
 cross-check the average launch durations."""
 import json
@@ -415,6 +420,107 @@ def fed_dp(out_path=None, reps=5, rounds=5, num_classes=101):
             f.write(text)
 
 
+def fed_q8(out_path=None, reps=5, rounds=5, num_classes=101):
+    """The compressed aggregation over VideoClassifier models at 112^2 that have each run one
+    forward, K = 4 and K = 8 selected clients: FedCohort.aggregate_q8 (one launch plus the counter
+    launch) without and with the payload, the plain FedCohort.aggregate, and the eager
+    q8_aggregate_reference over state_dicts, alternating in one process.  The launch's own time
+    comes from torch.profiler's trace of the same calls; GB/s against algorithmic bytes per
+    quantised element, 4 + 8 K read (theta, K sources, K residuals) and 4 K + 4 x destinations
+    written (K residuals, one destination), plus K x (1 + 4 / 256) for the payload ((K + 1) x 4 B
+    per element for the plain aggregate and for the unquantised entries).  Ends with the 4.9 GB
+    copy calibration; the ratio to it is recorded, the fused call must beat the eager reference."""
+    import statistics
+    from ssl_mae_amd.finetune import VideoClassifier
+    lines = [f"device: {torch.cuda.get_device_name(0)}; VideoClassifier({num_classes}) at 112^2; {rounds} rounds of "
+             f"{reps} aggregations (1 for the eager reference), median [min .. max]"]
+    clip = torch.randn(1, 3, 1, 112, 112, device="cuda")
+    models = []
+    for s in range(9):
+        torch.manual_seed(s)
+        m = VideoClassifier(num_classes, img_size=112).cuda().eval()
+        with torch.no_grad():
+            m(clip)
+        models.append(m)
+    glob = models[0]
+    results = []
+    for k in (4, 8):
+        clients = models[1:k + 1]
+        sel = list(range(k))
+        sizes = [100.0 + 10 * i for i in sel]
+        cohort = F.FedCohort(glob, clients)
+        state = glob.state_dict()
+        n_all = sum(state[key].numel() for key in cohort.float_keys)
+        n_q = sum(state[key].numel() for key, m in zip(cohort.float_keys, cohort._clip_modes) if m)
+        params = {name for name, _ in glob.named_parameters()}
+        residuals = [{} for _ in clients]
+
+        def q8():
+            cohort.aggregate_q8(sel, sizes)
+
+        def q8_payload():
+            cohort.aggregate_q8(sel, sizes, payload=True)
+
+        def plain():
+            cohort.aggregate(sel, sizes)
+
+        def reference():
+            states = [{n: v.detach() for n, v in c.state_dict().items()} for c in clients]
+            F.q8_aggregate_reference(glob, states, sizes, residuals)
+
+        for fn in (q8, q8_payload, plain, reference):
+            fn()
+        torch.cuda.synchronize()
+        tq, ty, tp, tr = [], [], [], []
+        for _ in range(rounds):                         # alternate the paths
+            tq += _rounds(q8, reps, 1)
+            ty += _rounds(q8_payload, reps, 1)
+            tp += _rounds(plain, reps, 1)
+            tr += _rounds(reference, 1, 1)
+        mq, mr = statistics.median(tq), statistics.median(tr)
+        gbq = ((4 + 8 * k + 4 * k + 4) * n_q + (k + 1) * 4 * (n_all - n_q)) / 1e9
+        gby = gbq + k * (1 + 4 / 256) * n_q / 1e9
+        gbp = (k + 1) * 4 * n_all / 1e9
+        lines.append(f"K={k} selected clients, {len(cohort.float_keys)} fp32 entries ({sum(cohort._clip_modes)} quantised), "
+                     f"{n_all} fp32 elements ({n_q} quantised) per model; one upload "
+                     f"{F.q8_upload_bytes(state, params) / 2 ** 20:.2f} MiB against {F.model_size_bytes(state) / 2 ** 20:.2f} "
+                     f"MiB in fp32:")
+        lines.append(f"  FedCohort.aggregate_q8: {_fmt(tq)}")
+        lines.append(f"  FedCohort.aggregate_q8, payload written: {_fmt(ty)}")
+        lines.append(f"  FedCohort.aggregate (plain FedAvg): {_fmt(tp)}")
+        lines.append(f"  q8_aggregate_reference (eager torch over state_dicts): {_fmt(tr)}  {mr / mq:.1f}x aggregate_q8")
+        try:
+            kq = _kernel_times(q8, reps, ("q8_exchange_kernel",))["q8_exchange_kernel"]
+            ky = _kernel_times(q8_payload, reps, ("q8_exchange_kernel",))["q8_exchange_kernel"]
+            kp = _kernel_times(plain, reps, ("fedavg_exchange_kernel",))["fedavg_exchange_kernel"]
+            q8_gbs = gbq / max(kq, 1e-9) * 1e3
+            lines.append(f"  launch of aggregate_q8: {kq:.3f} ms ({gbq:.3f} GB, {q8_gbs:.0f} GB/s); with the payload "
+                         f"{ky:.3f} ms ({gby:.3f} GB, {gby / max(ky, 1e-9) * 1e3:.0f} GB/s)")
+            lines.append(f"  launch of the plain aggregate: {kp:.3f} ms ({gbp:.3f} GB, {gbp / max(kp, 1e-9) * 1e3:.0f} GB/s)")
+        except Exception as exc:  # the trace splits the total; the totals above are the measurement
+            q8_gbs = float("nan")
+            lines.append(f"  launches: not measured ({type(exc).__name__}: {exc})")
+        results.append((k, mq, mr, q8_gbs))
+        assert cohort.rebuilds == 1
+    del models, clients, cohort, residuals
+    torch.cuda.empty_cache()
+    line, copy_gbs = _copy_calibration(rounds)
+    lines.append(line)
+    ok = True
+    for k, mq, mr, gq in results:
+        ok = ok and mq < mr
+        lines.append(f"K={k}: aggregate_q8 launch at {gq / copy_gbs:.2f} of the copy calibration's bandwidth; aggregate_q8 is "
+                     f"{'FASTER' if mq < mr else 'NOT faster'} than q8_aggregate_reference ({mq:.3f} ms against {mr:.3f} ms)")
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+    if not ok:
+        raise SystemExit("aggregate_q8 did not beat q8_aggregate_reference")
+
+
 def _count_launches(fn):
     """Device kernels / memsets / copies of one call, from torch.profiler's trace."""
     from torch.profiler import ProfilerActivity, profile
@@ -538,9 +644,9 @@ def finetune(out_path=None, reps=10, rounds=7, num_classes=101):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] in ("resize", "fedround", "finetune", "fed_dp"):
+    if len(sys.argv) > 1 and sys.argv[1] in ("resize", "fedround", "finetune", "fed_dp", "fed_q8"):
         out = sys.argv[3] if len(sys.argv) > 3 and sys.argv[2] == "--out" else None
-        {"resize": resize, "fedround": fedround, "finetune": finetune, "fed_dp": fed_dp}[sys.argv[1]](out)
+        {"resize": resize, "fedround": fedround, "finetune": finetune, "fed_dp": fed_dp, "fed_q8": fed_q8}[sys.argv[1]](out)
     else:
         main()
         frames()

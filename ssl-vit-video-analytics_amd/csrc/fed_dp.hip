@@ -25,34 +25,6 @@ using namespace fedtab;
 
 namespace {
 
-constexpr int kGroups = kChunk / (256 * 4);   // 4-element groups per lane per model
-static_assert(kChunk % 1024 == 0, "a chunk is a whole number of 256-lane float4 rows");
-
-// Elements [e0, e0 + 4) of a chunk of n elements at p: 16 bytes when the chunk is aligned (vec)
-// and the group is whole, else element by element; slots past n read as +0.
-SM_DEV f32x4 load_group(const float* p, int e0, int n, bool vec) {
-  if (vec && e0 + 4 <= n) return __builtin_nontemporal_load((const f32x4*)(p + e0));
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-    if (e0 + e < n) v[e] = p[e0 + e];
-  return v;
-}
-
-SM_DEV void store_group(float* q, int e0, int n, bool vec, f32x4 v) {
-  if (vec && e0 + 4 <= n) {
-    __builtin_nontemporal_store(v, (f32x4*)(q + e0));
-    return;
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-    if (e0 + e < n) q[e0 + e] = v[e];
-}
-
-SM_DEV const float* seg_ptr(const TableView& t, int model, int64_t seg, int64_t off) {
-  return (const float*)t.addr[model * t.S + seg] + off;
-}
-
 // One lane's share of sum (x - g)^2, groups then elements ascending (padding slots add +0).
 SM_DEV float lane_sq(const f32x4* x, const f32x4* g) {
   float s = 0.f;
@@ -146,14 +118,6 @@ SM_DEV void add_clipped(f32x4* acc, const f32x4* x, const f32x4* g, float ws) {
   for (int u = 0; u < kGroups; ++u)
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc[u][e] = __fadd_rn(acc[u][e], __fmul_rn(ws, __fsub_rn(x[u][e], g[u][e])));
-}
-
-// acc += x w: sm_fedavg_exchange's operations.
-SM_DEV void add_plain(f32x4* acc, const f32x4* x, float w) {
-#pragma unroll
-  for (int u = 0; u < kGroups; ++u)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[u][e] = __fadd_rn(acc[u][e], __fmul_rn(x[u][e], w));
 }
 
 // Sources, theta and destinations may alias: a lane loads its elements from theta and every

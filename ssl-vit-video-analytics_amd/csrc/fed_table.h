@@ -1,5 +1,5 @@
 // The FedAvg exchange table (include/sm_api.h "FedAvg exchange table") as the kernels of
-// csrc/fed.hip and csrc/fed_dp.hip see it, and the host-side check of a launch's arguments.
+// csrc/fed.hip, csrc/fed_dp.hip and csrc/fed_q8.hip see it, and the host-side check of a launch's arguments.
 #pragma once
 #include "common.h"
 #include "sm_api.h"
@@ -24,16 +24,22 @@ struct TableView {
   const int32_t* chunk_seg;  // [C]
 };
 
-SM_DEV TableView table_view(const unsigned char* tab) {
-  const SmFedTableHeader* h = (const SmFedTableHeader*)tab;
+// The view from the header's counts (the host has read them back: exchange_args).
+SM_DEV TableView table_view(const unsigned char* tab, int64_t P, int64_t S, int64_t C) {
   TableView t;
-  t.S = h->num_segments;
-  t.C = h->num_chunks;
+  t.S = S;
+  t.C = C;
   t.addr = (const uint64_t*)(tab + sizeof(SmFedTableHeader));
-  t.seg_len = (const int64_t*)(t.addr + h->num_models * t.S);
+  t.seg_len = (const int64_t*)(t.addr + P * t.S);
   t.chunk_off = t.seg_len + t.S;
   t.chunk_seg = (const int32_t*)(t.chunk_off + t.C);
   return t;
+}
+
+// The same from the header in device memory.
+SM_DEV TableView table_view(const unsigned char* tab) {
+  const SmFedTableHeader* h = (const SmFedTableHeader*)tab;
+  return table_view(tab, h->num_models, h->num_segments, h->num_chunks);
 }
 
 // Elements [off, off + n) of segment `seg`: false when the chunk entry points outside it.
@@ -45,6 +51,44 @@ SM_DEV bool chunk_range(const TableView& t, int64_t c, int64_t& seg, int64_t& of
   if (off >= len) return false;
   n = len - off < kChunk ? len - off : kChunk;
   return true;
+}
+
+// ---- a lane's share of a chunk in csrc/fed_dp.hip and csrc/fed_q8.hip: the 4-element groups tid and
+// tid + 256 of the chunk, in the 16-byte form and in the element-wise form alike.
+constexpr int kGroups = kChunk / (256 * 4);   // 4-element groups per lane per model
+static_assert(kChunk % 1024 == 0, "a chunk is a whole number of 256-lane float4 rows");
+
+// Elements [e0, e0 + 4) of a chunk of n elements at p: 16 bytes when the chunk is aligned (vec)
+// and the group is whole, else element by element; slots past n read as +0.
+SM_DEV f32x4 load_group(const float* p, int e0, int n, bool vec) {
+  if (vec && e0 + 4 <= n) return __builtin_nontemporal_load((const f32x4*)(p + e0));
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    if (e0 + e < n) v[e] = p[e0 + e];
+  return v;
+}
+
+SM_DEV void store_group(float* q, int e0, int n, bool vec, f32x4 v) {
+  if (vec && e0 + 4 <= n) {
+    __builtin_nontemporal_store(v, (f32x4*)(q + e0));
+    return;
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    if (e0 + e < n) q[e0 + e] = v[e];
+}
+
+SM_DEV const float* seg_ptr(const TableView& t, int model, int64_t seg, int64_t off) {
+  return (const float*)t.addr[model * t.S + seg] + off;
+}
+
+// acc += x w: sm_fedavg_exchange's operations.
+SM_DEV void add_plain(f32x4* acc, const f32x4* x, float w) {
+#pragma unroll
+  for (int u = 0; u < kGroups; ++u)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[u][e] = __fadd_rn(acc[u][e], __fmul_rn(x[u][e], w));
 }
 
 // Counts, model indices and the table's header (read back from the device: 64 bytes, once

@@ -152,6 +152,8 @@ _SIGS = {
     "sm_fedavg_dp_exchange_workspace_bytes": (_c_i64, [_c_i32, _c_i64]),
     "sm_fedavg_dp_exchange": (_c_i32, [_c_i32, _c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p, _c_i64, _c_p, _c_f32, _c_f32,
                                        _c_u64, _c_p, _c_p, _c_i64, _c_p]),
+    "sm_fedavg_q8_exchange": (_c_i32, [_c_i32, _c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i32,
+                                       _c_p, _c_p, _c_p, _c_p]),
     "sm_frames_normalize": (_c_i32, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_i32, _c_p, _c_p]),
     "sm_frames_resize_normalize": (_c_i32, [_c_p, _c_p, _c_i64, _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_i32,
                                             _c_p, _c_p]),

@@ -24,6 +24,12 @@ global model's parameters, averages the clipped updates and adds Gaussian noise 
 the numpy statement the tests compare bits with, `dp_epsilon` the RDP accountant's estimate.
 BatchNorm running statistics keep plain FedAvg and are outside the guarantee.
 
+Compressed uploads (not in the reference): `FedCohort.aggregate_q8` quantises every client's update
+over the global model's parameters to int8 with one fp32 scale per 256 elements and keeps the
+quantisation error as the client's residual for its next update (error feedback), in one launch
+(sm_fedavg_q8_exchange); `q8_aggregate_reference` is the same in eager torch, `q8_aggregate_mirror`
+the numpy statement the tests compare bits with, `q8_upload_bytes` the wire size of one upload.
+
 Multi-GPU (BASELINE config C5, 4 clients on 4 GPUs): `fedavg_allgather` makes
 every rank one client.  Each rank's flat fp32 state is all-gathered over RCCL
 (one collective per round, (N-1) x 80 MiB per rank over xGMI ~ 2 ms at N=4),
@@ -203,6 +209,7 @@ class FedCohort:
         self._clip_modes = [1 if k in params else 0 for k in self.float_keys]
         self._float_chunks = sum(-(-ref[k].numel() // K.FEDAVG_CHUNK_ELEMS) for k in self.float_keys)
         self.rebuilds = 0
+        self._resid = None        # aggregate_q8's residuals, one row per client
         self._build()
 
     def _entries(self, p):
@@ -224,12 +231,14 @@ class FedCohort:
                         for k, a in zip(self.count_keys, self._count_addr[p * nc:(p + 1) * nc])))
 
     @torch.no_grad()
-    def exchange(self, src, weights, dst, copy_only=False, dp=None):
+    def exchange(self, src, weights, dst, copy_only=False, dp=None, q8=None):
         """Table-model indices: sources (in accumulation order), their normalised fp32 weights,
         destinations.  dp = (clip_norm, noise_std, seed): the fp32 entries go through
         sm_fedavg_dp_exchange against the global model (table model 0) instead, and the device
-        `stats` tensor (the sources' update norms, then their clip scales) is returned."""
-        ents = {p: self._entries(p) for p in dict.fromkeys(list(src) + list(dst) + ([0] if dp else []))}
+        `stats` tensor (the sources' update norms, then their clip scales) is returned.
+        q8 = (codes, scales), either None: they go through sm_fedavg_q8_exchange with the cohort's
+        residuals instead, and the device `part` tensor is returned."""
+        ents = {p: self._entries(p) for p in dict.fromkeys(list(src) + list(dst) + ([0] if dp or q8 else []))}
         if not all(self._fresh(p, e) for p, e in ents.items()):
             self._build()
         stats = None
@@ -240,6 +249,12 @@ class FedCohort:
             stats = K.fedavg_dp_exchange([ents[p][k].detach() for p in dst for k in self.float_keys], src, weights, 0,
                                          dst, self._float_table, self._float_chunks, self._seg_clip, clip_norm,
                                          noise_std, seed)
+        elif q8 is not None:
+            if not self.float_keys:
+                raise RuntimeError("[ERROR] FedCohort: compressed FedAvg needs fp32 state entries")
+            stats = K.fedavg_q8_exchange([ents[p][k].detach() for p in dst for k in self.float_keys], src, weights, 0,
+                                         dst, self._float_table, self._float_chunks, self._seg_clip,
+                                         self._residuals(), q8[0], q8[1])
         elif self.float_keys:
             K.fedavg_exchange([ents[p][k].detach() for p in dst for k in self.float_keys], src, weights, dst,
                               self._float_table, copy_only)
@@ -266,6 +281,42 @@ class FedCohort:
         norm = _norm_weights(client_weights, total_w)
         return self.exchange(self._clients(selected), norm, [0] + self._clients(also),
                              dp=(float(clip_norm), dp_noise_std(norm, clip_norm, noise_multiplier), int(seed)))
+
+    def _residuals(self):
+        device = self._float_table.device
+        if self._resid is None:
+            self._resid = torch.zeros((len(self.client_models), self._float_chunks * K.FEDAVG_CHUNK_ELEMS),
+                                      dtype=torch.float32, device=device)
+        elif self._resid.device != device:          # the cohort moved: the residuals follow it
+            self._resid = self._resid.to(device)
+        return self._resid
+
+    def reset_residuals(self):
+        """Zeroes every client's quantisation residual."""
+        if self._resid is not None:
+            self._resid.zero_()
+
+    def aggregate_q8(self, selected, client_weights, also=(), payload=False):
+        """Compressed FedAvg of the clients `selected` into the global model and the clients `also`:
+        over the global model's parameters each client's update x_c - theta plus its residual is
+        quantised to int8 with one fp32 scale per 256 elements, the dequantised updates are
+        averaged onto theta with the normalised weights, and the quantisation error becomes the
+        client's residual (one row per client, owned by the cohort, zero at first, indexed by
+        chunk so it survives a table rebuild), in one launch (sm_fedavg_q8_exchange).  Float
+        buffers, the BatchNorm running statistics, keep plain FedAvg in fp32, as do the integer
+        entries' rules.
+        -> the device tensor fp64 [len(selected), chunks, 2]: per chunk, max |update + residual| and
+        the sum of squares of the new residual; with payload=True (part, (codes, scales)), what the
+        clients upload: int8 [len(selected), chunks, 2048] and fp32 [len(selected), chunks, 8]."""
+        total_w = _check(selected, client_weights)
+        norm = _norm_weights(client_weights, total_w)
+        q8 = (None, None)
+        if payload:
+            device, k, C = self._float_table.device, len(selected), self._float_chunks
+            q8 = (torch.empty((k, C, K.FEDAVG_CHUNK_ELEMS), dtype=torch.int8, device=device),
+                  torch.empty((k, C, K.FEDAVG_CHUNK_ELEMS // Q8_BLOCK), dtype=torch.float32, device=device))
+        part = self.exchange(self._clients(selected), norm, [0] + self._clients(also), q8=q8)
+        return (part, q8) if payload else part
 
     def aggregate(self, selected, client_weights, also=()):
         """FedAvg of the clients `selected` (in that order) into the global model and into the
@@ -458,6 +509,205 @@ def dp_epsilon(noise_multiplier, sample_rate, rounds, delta, orders=range(2, 256
     return best
 
 
+# ------------------------------------------------------------------ compressed uploads (not in the reference)
+Q8_BLOCK = K.FEDAVG_Q8_BLOCK    # elements per scale
+_Q8_LIVE = 1e-30          # a block whose largest |v| is below this (or not finite) is not quantised
+
+
+def q8_upload_bytes(state, params):
+    """The wire size of one client's compressed upload: an entry named in `params` (the quantised
+    ones, the global model's parameters) takes one byte per element plus one fp32 scale per block
+    of 256; every other entry goes as it is."""
+    total = 0
+    for k, v in state.items():
+        if not torch.is_tensor(v):
+            continue
+        n = v.numel()
+        total += n + 4 * (-(-n // Q8_BLOCK)) if k in params and _is_float_tensor(v) else n * v.element_size()
+    return int(total)
+
+
+def _q8_check(compress, dp):
+    if compress is None:
+        return
+    if dp is not None:
+        raise ValueError("[ERROR] FedAvg: dp and compress are exclusive (quantising a clipped, noised aggregate "
+                         "changes the sensitivity analysis)")
+    if compress.get("method") != "q8":
+        raise ValueError(f"[ERROR] FedAvg: unknown compression method {compress.get('method')!r} (q8)")
+
+
+def _q8_chunk_part(m_blocks, e_new, n):
+    """The kernel's chunk statistics of one entry from its block maxima and new residual (flat,
+    n elements), in the kernel's order: a lane's 8 squares in fp32, ascending; the 64 lanes of a
+    wave by the xor butterfly and the 4 waves in order in fp64.  -> fp64 [chunks, 2]."""
+    chunk = K.FEDAVG_CHUNK_ELEMS
+    C = -(-n // chunk)
+    per = chunk // Q8_BLOCK
+    mx = torch.nn.functional.pad(m_blocks, (0, C * per - m_blocks.numel())).view(C, per).max(dim=1).values
+    E = torch.nn.functional.pad(e_new, (0, C * chunk - n)).view(C, chunk // 1024, 256, 4)
+    sq = E * E
+    s = torch.zeros((C, 256), dtype=torch.float32, device=e_new.device)
+    for u in range(chunk // 1024):
+        for i in range(4):
+            s = s + sq[:, u, :, i]
+    sd = s.double().view(C, 4, 64)
+    lanes = torch.arange(64, device=e_new.device)
+    for o in (32, 16, 8, 4, 2, 1):
+        sd = sd + sd[:, :, lanes ^ o]
+    w = sd[:, :, 0]
+    return torch.stack([mx.double(), ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]], dim=1)
+
+
+def q8_aggregate_reference(global_model, client_states, client_weights, residuals):
+    """Compressed FedAvg in eager torch over state_dicts, the mathematics of FedCohort.aggregate_q8
+    entry by entry with one individually rounded torch op per kernel operation: the global model's
+    float parameters are quantised in blocks of 256 (an entry is padded with zeros to whole blocks
+    for the block maximum), float buffers take fedavg_aggregate's weighted sum, num_batches_tracked
+    the max, other integer entries the first client's value.  `residuals` is a list of per-client
+    dicts {key: fp32 tensor}, one per client state, updated in place (a missing key starts at
+    zero).  Loads the result into `global_model` (strict) and returns (the new state dict, the fp64
+    [K, chunks, 2] tensor FedCohort.aggregate_q8 returns).  It serves `federated.exchange:
+    reference` and is the baseline the fused exchange is timed against."""
+    total_w = _check(client_states, client_weights)
+    if len(residuals) != len(client_states):
+        raise RuntimeError("[ERROR] q8_aggregate_reference: one residual dict per client state")
+    norm = _norm_weights(client_weights, total_w)
+    global_state = global_model.state_dict()
+    device = _device_of(global_model, global_state)
+    params = {k for k, _ in global_model.named_parameters(remove_duplicate=False)}
+    float_keys = [k for k, v in global_state.items() if _is_float_tensor(v)]
+    for k in float_keys:
+        if global_state[k].dtype != torch.float32 or any(k not in cs for cs in client_states):
+            raise RuntimeError(f"[ERROR] compressed FedAvg needs {k} as fp32 in every client state")
+    f32 = dict(dtype=torch.float32, device=device)
+    live_min = torch.tensor(_Q8_LIVE, **f32)
+    c127 = torch.tensor(127.0, dtype=torch.float64, device=device)      # a device tensor: a true division
+    zero = torch.zeros((), **f32)
+    chunk = K.FEDAVG_CHUNK_ELEMS
+
+    new_state, parts = {}, [[] for _ in client_states]
+    for k, g in global_state.items():
+        if k in params and _is_float_tensor(g):
+            theta = g.detach().reshape(-1)
+            n = theta.numel()
+            nb = -(-n // Q8_BLOCK)
+            acc = theta.clone()
+            for c, cs in enumerate(client_states):
+                if k not in residuals[c]:
+                    residuals[c][k] = torch.zeros_like(g.detach())
+                e = residuals[c][k]
+                v = (cs[k].detach().to(device).reshape(-1) - theta) + e.reshape(-1)
+                vb = torch.nn.functional.pad(v, (0, nb * Q8_BLOCK - n)).view(nb, Q8_BLOCK)
+                m = vb.abs().max(dim=1).values                         # a NaN in a block makes m NaN
+                live = (m >= live_min) & torch.isfinite(m)
+                # an fp32 quotient formed in fp64 and rounded once more is the correctly rounded fp32
+                # quotient (53 >= 2 * 24 + 2 bits), whatever the backend's fp32 division does
+                s = torch.where(live, (m.double() / c127).float(), zero)
+                inv = torch.where(live, (c127 / m.double()).float(), zero)
+                q = torch.where(live[:, None], torch.clamp(torch.round(vb * inv[:, None]), -127.0, 127.0), zero)
+                d = q * s[:, None]
+                e_new = (vb - d).reshape(-1)[:n]
+                acc = acc + (d.reshape(-1)[:n] * norm[c])
+                e.copy_(e_new.view(e.shape))
+                parts[c].append(_q8_chunk_part(m, e_new, n))
+            new_state[k] = acc.view(g.shape)
+        elif _is_float_tensor(g):
+            acc = torch.zeros_like(g.detach())
+            for cs, w in zip(client_states, norm):
+                acc += cs[k].detach().to(device) * w
+            new_state[k] = acc
+            for p in parts:
+                p.append(torch.zeros((-(-g.numel() // chunk), 2), dtype=torch.float64, device=device))
+        elif any(k not in cs for cs in client_states):
+            new_state[k] = g.detach().clone()
+        elif "num_batches_tracked" in k:
+            new_state[k] = torch.stack([cs[k].detach().to(device) for cs in client_states]).max(dim=0).values
+        else:
+            new_state[k] = client_states[0][k].detach().to(device).clone()
+    global_model.load_state_dict(new_state, strict=True)
+    return new_state, torch.stack([torch.cat(p) for p in parts])
+
+
+def q8_aggregate_mirror(theta, sources, residuals, norm_weights, seg_modes, with_part=False):
+    """Host mirror (numpy) of sm_fedavg_q8_exchange, one operation at a time in np.float32 (add,
+    subtract, multiply and divide are correctly rounded, np.rint rounds half to even).  theta: S
+    fp32 arrays; sources and residuals: K lists of S fp32 arrays; norm_weights: the K normalised
+    fp32 weights; seg_modes: S modes.  -> (the S result arrays, the K lists of S new residuals, the
+    K lists of S int8 code arrays, the K lists of S fp32 scale arrays, one scale per block of 256);
+    a mode-0 segment keeps its residual and has codes and scales of zeros.  with_part adds the
+    kernel's `part`, fp64 [K, chunks, 2]."""
+    f32 = np.float32
+    chunk = K.FEDAVG_CHUNK_ELEMS
+    theta = [np.asarray(t, dtype=f32) for t in theta]
+    w = [f32(x) for x in norm_weights]
+    out, new_res, codes, scales = [], [[] for _ in sources], [[] for _ in sources], [[] for _ in sources]
+    parts = [[] for _ in sources]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore", under="ignore"):
+        for s, (t, mode) in enumerate(zip(theta, seg_modes)):
+            n = t.size
+            nb, C = -(-n // Q8_BLOCK), -(-n // chunk)
+            if not mode:
+                acc = np.zeros_like(t)
+                for c, src in enumerate(sources):
+                    acc = acc + np.asarray(src[s], dtype=f32) * w[c]
+                    new_res[c].append(np.asarray(residuals[c][s], dtype=f32).copy())
+                    codes[c].append(np.zeros(n, dtype=np.int8))
+                    scales[c].append(np.zeros(nb, dtype=f32))
+                    parts[c].append(np.zeros((C, 2)))
+                out.append(acc)
+                continue
+            acc = t.copy()
+            for c, src in enumerate(sources):
+                v = (np.asarray(src[s], dtype=f32) - t) + np.asarray(residuals[c][s], dtype=f32)
+                vb = np.zeros(nb * Q8_BLOCK, dtype=f32)
+                vb[:n] = v
+                vb = vb.reshape(nb, Q8_BLOCK)
+                m = np.max(np.abs(vb), axis=1)                      # np.max propagates a NaN
+                live = (m >= f32(_Q8_LIVE)) & np.isfinite(m)
+                safe = np.where(live, m, f32(1.0))
+                sc = np.where(live, safe / f32(127.0), f32(0.0)).astype(f32)
+                inv = np.where(live, f32(127.0) / safe, f32(0.0)).astype(f32)
+                q = np.where(live[:, None], np.clip(np.rint(vb * inv[:, None]), f32(-127.0), f32(127.0)), f32(0.0))
+                q = q.astype(f32)
+                d = q * sc[:, None]
+                e_new = (vb - d).reshape(-1)
+                acc = acc + w[c] * d.reshape(-1)[:n]
+                new_res[c].append(e_new[:n].copy())
+                codes[c].append(q.reshape(-1)[:n].astype(np.int8))
+                scales[c].append(sc)
+                if with_part:
+                    parts[c].append(_q8_chunk_part_np(m, e_new, n))
+            out.append(acc)
+    if with_part:
+        return out, new_res, codes, scales, np.stack([np.concatenate(p) for p in parts])
+    return out, new_res, codes, scales
+
+
+def _q8_chunk_part_np(m_blocks, e_new, n):
+    """_q8_chunk_part in numpy: e_new is the entry's new residual padded with zeros to whole blocks."""
+    f32 = np.float32
+    chunk = K.FEDAVG_CHUNK_ELEMS
+    C, per = -(-n // chunk), chunk // Q8_BLOCK
+    mb = np.zeros(C * per, dtype=f32)
+    mb[:m_blocks.size] = m_blocks
+    E = np.zeros(C * chunk, dtype=f32)
+    E[:e_new.size] = e_new
+    E = E.reshape(C, chunk // 1024, 256, 4)
+    sq = E * E
+    s = np.zeros((C, 256), dtype=f32)
+    for u in range(chunk // 1024):
+        for i in range(4):
+            s = s + sq[:, u, :, i]
+    sd = s.astype(np.float64).reshape(C, 4, 64)
+    lanes = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        sd = sd + sd[:, :, lanes ^ o]
+    wv = sd[:, :, 0]
+    return np.stack([np.max(mb.reshape(C, per), axis=1).astype(np.float64),
+                     ((wv[:, 0] + wv[:, 1]) + wv[:, 2]) + wv[:, 3]], axis=1)
+
+
 # ------------------------------------------------------------------ multi-GPU (C5)
 def fedavg_allgather(model, weight, group=None, combine=None):
     """Every rank is one client: replace `model`'s state on every rank with the
@@ -562,20 +812,51 @@ def _dp_round(log, r, rec, stats, selected, weights, dp):
     return rec
 
 
+def _q8_round(log, r, rec, part, selected, global_model, global_state):
+    """One read-back of the round's compression statistics (per client, the largest chunk maximum
+    and the sum of the chunks' residual squares, reduced on `part`'s device): a non-finite maximum
+    raises, naming the client; comm_mb_round becomes the fp32 broadcast plus the compressed upload,
+    and the record gains upload_mb_fp32 / upload_mb_q8 / q8_absmax / q8_resid_norm and the log one
+    line."""
+    mx, sq = torch.stack([part[:, :, 0].amax(dim=1), part[:, :, 1].sum(dim=1)]).tolist()
+    for cid, m in zip(selected, mx):
+        if not math.isfinite(m):
+            raise RuntimeError(f"[ERROR] Round {r}: the update of client {cid} has a non-finite element "
+                               f"(largest |update + residual| = {m})")
+    k = len(selected)
+    params = {name for name, _ in global_model.named_parameters(remove_duplicate=False)}
+    fp32_mb = bytes_to_mb(k * model_size_bytes(global_state))
+    rec["upload_mb_fp32"] = float(fp32_mb)
+    rec["upload_mb_q8"] = float(bytes_to_mb(k * q8_upload_bytes(global_state, params)))
+    rec["comm_mb_round"] = float(fp32_mb + rec["upload_mb_q8"])
+    rec["q8_absmax"] = float(max(mx))
+    rec["q8_resid_norm"] = float(math.sqrt(sum(sq)))
+    log(f"[INFO] Round {r} upload_mb_q8={rec['upload_mb_q8']:.2f} upload_mb_fp32={fp32_mb:.2f} "
+        f"comm_mb={rec['comm_mb_round']:.2f} q8_absmax={rec['q8_absmax']:.6f} "
+        f"q8_resid_norm={rec['q8_resid_norm']:.6f}")
+    return rec
+
+
 def run_fedavg(global_model, client_models, client_loaders, client_sizes, evaluate_fn, device, rounds=10,
-               client_fraction=1.0, amp=True, log_f=None, dp=None):
+               client_fraction=1.0, amp=True, log_f=None, dp=None, compress=None):
     """fed_loop.py:65-150: each round samples clients with random.Random(42),
     broadcasts the global weights, runs client_loaders[cid]["update_fn"](model),
     aggregates with fedavg_aggregate and evaluates.  Returns the per-round records.
     dp = {"clip_norm", "noise_multiplier", "seed"}: the round aggregates with
     dp_aggregate_reference under dp_round_seed(seed, r) instead, and its record and log carry the
-    DP statistics (_dp_round)."""
+    DP statistics (_dp_round).
+    compress = {"method": "q8", "error_feedback": bool}: the round aggregates with
+    q8_aggregate_reference over per-client residuals kept here (zeroed before every round when
+    error_feedback is false), and its record carries the compressed upload (_q8_round).  dp and
+    compress together raise ValueError."""
+    _q8_check(compress, dp)
     if dp is not None:
         _dp_check(dp["clip_norm"], dp["noise_multiplier"])
     num_clients = len(client_models)
     rng = random.Random(42)
     records = []
     log = functools.partial(log_line, log_f)
+    residuals = [{} for _ in range(num_clients)]
 
     for r in range(1, int(rounds) + 1):
         m = max(1, int(num_clients * float(client_fraction)))
@@ -589,7 +870,12 @@ def run_fedavg(global_model, client_models, client_loaders, client_sizes, evalua
             losses.append(float(client_loaders[cid]["update_fn"](client_models[cid])))
             states.append({k: v.detach() for k, v in client_models[cid].state_dict().items()})
             weights.append(float(client_sizes[cid]))
-        if dp is None:
+        if compress is not None:
+            if not compress.get("error_feedback", True):
+                for res in residuals:
+                    res.clear()
+            new_state, part = q8_aggregate_reference(global_model, states, weights, [residuals[cid] for cid in selected])
+        elif dp is None:
             new_state = fedavg_aggregate(global_model, states, weights)
         else:
             new_state, stats = dp_aggregate_reference(global_model, states, weights, dp["clip_norm"],
@@ -598,15 +884,19 @@ def run_fedavg(global_model, client_models, client_loaders, client_sizes, evalua
         records.append(_round_record(log, r, selected, losses, new_state, top1, top5))
         if dp is not None:
             _dp_round(log, r, records[-1], stats, selected, weights, dp)
+        if compress is not None:
+            _q8_round(log, r, records[-1], part, selected, global_model, new_state)
     return records
 
 
 def run_fedavg_fused(global_model, client_models, client_loaders, client_sizes, evaluate_fn, device, rounds=10,
-                     client_fraction=1.0, amp=True, log_f=None, dp=None):
+                     client_fraction=1.0, amp=True, log_f=None, dp=None, compress=None):
     """run_fedavg with the round's exchange through a FedCohort: the same sampled clients, log
     lines and records, and bit-identical model states, with one broadcast launch and one
     aggregation launch per round in place of the state_dict copies.  With `dp` (as run_fedavg's)
-    the aggregation is FedCohort.aggregate_dp."""
+    the aggregation is FedCohort.aggregate_dp, with `compress` FedCohort.aggregate_q8 over the
+    cohort's residuals."""
+    _q8_check(compress, dp)
     if dp is not None:
         _dp_check(dp["clip_norm"], dp["noise_multiplier"])
     num_clients = len(client_models)
@@ -622,7 +912,11 @@ def run_fedavg_fused(global_model, client_models, client_loaders, client_sizes, 
         cohort.broadcast(selected)
         losses = [float(client_loaders[cid]["update_fn"](client_models[cid])) for cid in selected]
         weights = [float(client_sizes[cid]) for cid in selected]
-        if dp is None:
+        if compress is not None:
+            if not compress.get("error_feedback", True):
+                cohort.reset_residuals()
+            part = cohort.aggregate_q8(selected, weights)
+        elif dp is None:
             cohort.aggregate(selected, weights)
         else:
             stats = cohort.aggregate_dp(selected, weights, dp["clip_norm"], dp["noise_multiplier"],
@@ -631,4 +925,6 @@ def run_fedavg_fused(global_model, client_models, client_loaders, client_sizes, 
         records.append(_round_record(log, r, selected, losses, global_model.state_dict(), top1, top5))
         if dp is not None:
             _dp_round(log, r, records[-1], stats, selected, weights, dp)
+        if compress is not None:
+            _q8_round(log, r, records[-1], part, selected, global_model, global_model.state_dict())
     return records

@@ -1167,6 +1167,58 @@ def fedavg_dp_exchange(src_models, weights, global_model, dst_models, table, num
     return stats
 
 
+FEDAVG_Q8_BLOCK = 256                        # SM_FEDAVG_Q8_BLOCK
+
+
+def fedavg_q8_exchange(src_models, weights, global_model, dst_models, table, num_chunks, seg_mode, resid,
+                       codes=None, scales=None, part=None):
+    """Compressed FedAvg over an fp32 cohort table (sm_fedavg_q8_exchange, include/sm_api.h): over
+    the segments whose `seg_mode` byte is 1 every source's update against model `global_model`, plus
+    its residual row, is quantised to int8 with one fp32 scale per 256-element block, the
+    dequantised updates are averaged with the normalised `weights` onto the global model and the
+    quantisation errors go back into `resid` (fp32 [rows, num_chunks * 2048], row = model index - 1);
+    segments with byte 0 get the plain weighted sum.  The result goes into every destination model.
+    codes (int8 [sources, num_chunks, 2048]) and scales (fp32 [sources, num_chunks, 8]) receive what
+    the clients upload when both are given.
+    -> part, fp64 [sources, num_chunks, 2] on the device: per chunk, max |v| and the sum of squares
+    of the new residual."""
+    import ctypes
+    _chk(table, seg_mode, resid, codes, scales, part)
+    name = "fedavg_q8_exchange"
+    if table.dtype != torch.uint8 or not table.is_contiguous():
+        raise _lib.KernelError(f"{name}: the table is a contiguous uint8 device tensor (fedavg_exchange_table)")
+    if len(weights) != len(src_models):
+        raise _lib.KernelError(f"{name}: {len(src_models)} sources but {len(weights)} weights")
+    if seg_mode is not None and (seg_mode.dtype != torch.uint8 or not seg_mode.is_contiguous()):
+        raise _lib.KernelError(f"{name}: seg_mode is a contiguous uint8 device tensor")
+    k, C = len(src_models), int(num_chunks)
+    rows = 0
+    if resid is not None:
+        if (resid.dtype != torch.float32 or resid.dim() != 2 or resid.shape[1] != C * FEDAVG_CHUNK_ELEMS
+                or not resid.is_contiguous()):
+            raise _lib.KernelError(f"{name}: resid must be contiguous fp32 [rows, {C * FEDAVG_CHUNK_ELEMS}]")
+        rows = resid.shape[0]
+    if codes is not None and (codes.dtype != torch.int8 or codes.numel() != k * C * FEDAVG_CHUNK_ELEMS
+                              or not codes.is_contiguous()):
+        raise _lib.KernelError(f"{name}: codes must be contiguous int8 [{k}, {C}, {FEDAVG_CHUNK_ELEMS}]")
+    n_scales = k * C * (FEDAVG_CHUNK_ELEMS // FEDAVG_Q8_BLOCK)
+    if scales is not None and (scales.dtype != torch.float32 or scales.numel() != n_scales
+                               or not scales.is_contiguous()):
+        raise _lib.KernelError(f"{name}: scales must be contiguous fp32 [{k}, {C}, "
+                               f"{FEDAVG_CHUNK_ELEMS // FEDAVG_Q8_BLOCK}]")
+    if part is None:
+        part = torch.empty((max(k, 1), C, 2), dtype=torch.float64, device=table.device)
+    elif part.dtype != torch.float64 or part.numel() != 2 * k * C or not part.is_contiguous():
+        raise _lib.KernelError(f"{name}: part must be contiguous fp64 [{k}, {C}, 2]")
+    src = (ctypes.c_int32 * max(1, k))(*[int(i) for i in src_models])
+    dst = (ctypes.c_int32 * max(1, len(dst_models)))(*[int(i) for i in dst_models])
+    wts = (ctypes.c_float * max(1, k))(*[float(w) for w in weights])
+    call("sm_fedavg_q8_exchange", k, ctypes.cast(src, ctypes.c_void_p), ctypes.cast(wts, ctypes.c_void_p),
+         int(global_model), len(dst_models), ctypes.cast(dst, ctypes.c_void_p), ptr(table), table.numel(),
+         ptr(seg_mode), ptr(resid), int(rows), ptr(codes), ptr(scales), ptr(part), stream())
+    return part
+
+
 # ------------------------------------------------------------------ clip input pipeline
 def frames_normalize(frames, mean, std, bgr_swap=True, valid=None, out=None):
     """uint8 [B,T,H,W,3] decoded frames -> fp32 [B,3,T,H,W] normalised clip

@@ -1309,6 +1309,7 @@ def fedavg_counters_max(bufs):
 
 FEDAVG_MAX_CLIENTS = _K.FEDAVG_MAX_CLIENTS
 FEDAVG_CHUNK_ELEMS = _K.FEDAVG_CHUNK_ELEMS
+FEDAVG_Q8_BLOCK = _K.FEDAVG_Q8_BLOCK
 fedavg_exchange_table = _K.fedavg_exchange_table     # host-side table build and upload, no launch
 
 
@@ -1364,6 +1365,32 @@ def fedavg_dp_exchange(tensors, src_models, weights, global_model, dst_models, t
                                          int(global_model), [int(i) for i in dst_models], table, int(num_chunks),
                                          seg_clip, float(clip_norm), float(noise_std), _s64(seed), stats)
     return stats
+
+
+# `tensors` as for fedavg_exchange; the residual rows, the optional payload and `part` are written too.
+@_op("fedavg_q8_exchange", "(Tensor(a!)[] tensors, int[] src_models, float[] weights, int global_model, "
+                           "int[] dst_models, Tensor table, int num_chunks, Tensor seg_mode, Tensor(b!) resid, "
+                           "Tensor(c!)? codes, Tensor(d!)? scales, Tensor(e!) part) -> ()",
+     ("tensors", "resid", "codes", "scales", "part"))
+def _fedavg_q8_exchange(tensors, src_models, weights, global_model, dst_models, table, num_chunks, seg_mode, resid,
+                        codes, scales, part):
+    _K.fedavg_q8_exchange(list(src_models), list(weights), global_model, list(dst_models), table, num_chunks,
+                          seg_mode, resid, codes, scales, part)
+
+
+_fedavg_q8_exchange.register_fake(_none)
+
+
+def fedavg_q8_exchange(tensors, src_models, weights, global_model, dst_models, table, num_chunks, seg_mode, resid,
+                       codes=None, scales=None, part=None):
+    """-> part, fp64 [sources, num_chunks, 2] on the device: per chunk, max |v| and the sum of
+    squares of the new residual."""
+    if part is None:
+        part = torch.empty((len(src_models), int(num_chunks), 2), dtype=torch.float64, device=table.device)
+    torch.ops.ssl_mae.fedavg_q8_exchange(list(tensors), [int(i) for i in src_models], [float(w) for w in weights],
+                                         int(global_model), [int(i) for i in dst_models], table, int(num_chunks),
+                                         seg_mode, resid, codes, scales, part)
+    return part
 
 
 @_op("frames_normalize", "(Tensor frames, float[] mean, float[] std, bool bgr_swap, Tensor? valid) -> Tensor")

@@ -14,6 +14,11 @@ state_dict path, with bit-identical model states.  `federated.dp.enabled: true` 
 aggregation into DP-FedAvg (clipped client updates, Gaussian noise on the aggregate; federated.
 FedCohort.aggregate_dp / dp_aggregate_reference) and adds fed_dp_summary.csv with the round's
 clipping statistics and the accountant's cumulative epsilon ESTIMATE (federated.dp_epsilon).
+`federated.compress.enabled: true` uploads every client's update as int8 codes with one fp32 scale
+per 256 elements, with error feedback (federated.FedCohort.aggregate_q8 / q8_aggregate_reference):
+fed_summary.csv and system_privacy_summary.csv then carry the compressed communication, and
+fed_compress_summary.csv the round's upload sizes and quantisation statistics.  DP and compression
+are exclusive.
 
 `make_class_shard_splits` / `read_split` / `write_split` are src/datasets/federated_split.py
 (same random.Random(seed) call order: the same seed writes the same files), `client_update` is
@@ -41,6 +46,8 @@ FED_COLUMNS = ("round", "val_top1", "val_top5", "avg_local_loss", "clients", "mo
 CENTRALIZED_COLUMNS = ("epoch", "train_loss", "val_top1", "val_top5")
 SYSTEM_COLUMNS = ("raw_upload_mb_est", "fed_comm_total_mb", "reduction_ratio")
 DP_COLUMNS = ("round", "clients", "dp_clipped", "dp_norm_mean", "dp_norm_max", "dp_noise_std", "epsilon_est", "delta")
+COMPRESS_COLUMNS = ("round", "clients", "upload_mb_fp32", "upload_mb_q8", "upload_ratio", "q8_absmax", "q8_resid_norm")
+COMPRESS_METHODS = ("q8",)
 EXCHANGES = {"fused": run_fedavg_fused, "reference": run_fedavg}
 
 DEFAULTS = {
@@ -52,7 +59,9 @@ DEFAULTS = {
                   "non_iid": {"enabled": True, "strategy": "class_shard", "shards_per_client": 6,
                               "min_samples_per_client": 200},
                   # DP-FedAvg; seed None: runtime.seed
-                  "dp": {"enabled": False, "clip_norm": 1.0, "noise_multiplier": 0.0, "delta": 1e-5, "seed": None}},
+                  "dp": {"enabled": False, "clip_norm": 1.0, "noise_multiplier": 0.0, "delta": 1e-5, "seed": None},
+                  # int8 block-quantised uploads; error_feedback false drops the residuals every round
+                  "compress": {"enabled": False, "method": "q8", "error_feedback": True}},
     # None: the federated value (epochs: rounds * local_epochs, the same training budget)
     "centralized": {"enabled": True, "epochs": None, "batch_size": None, "lr": None, "weight_decay": None},
     "system_privacy": {"estimate_raw_upload": True, "raw_dtype_bytes": 1},
@@ -83,6 +92,13 @@ def resolve_config(cfg, save_dir=None, exchange=None):
     if not float(dp["clip_norm"]) > 0.0 or not float(dp["noise_multiplier"]) >= 0.0 \
             or not 0.0 < float(dp["delta"]) < 1.0:
         raise ValueError("[ERROR] federated.dp: clip_norm > 0, noise_multiplier >= 0, 0 < delta < 1")
+    comp = fed["compress"]
+    if comp["method"] not in COMPRESS_METHODS:
+        raise ValueError(f"[ERROR] Unknown federated.compress.method: {comp['method']}, must be one of "
+                         f"{sorted(COMPRESS_METHODS)}")
+    if bool(dp["enabled"]) and bool(comp["enabled"]):
+        raise ValueError("[ERROR] federated.dp and federated.compress are exclusive: quantising a clipped, noised "
+                         "aggregate changes the sensitivity analysis")
     return out
 
 
@@ -251,6 +267,18 @@ def dp_summary_rows(records, dp, num_clients):
     return rows
 
 
+def compress_summary_rows(records):
+    """The rows of fed_compress_summary.csv: the round's fp32 and compressed upload sizes, their
+    ratio, and the quantiser's statistics (the largest |update + residual| over the clients, the
+    L2 norm of all their new residuals)."""
+    return [{"round": r["round"], "clients": int(r["clients"]),
+             "upload_mb_fp32": round(float(r["upload_mb_fp32"]), 6),
+             "upload_mb_q8": round(float(r["upload_mb_q8"]), 6),
+             "upload_ratio": round(float(r["upload_mb_q8"]) / float(r["upload_mb_fp32"]), 6),
+             "q8_absmax": round(float(r["q8_absmax"]), 6),
+             "q8_resid_norm": round(float(r["q8_resid_norm"]), 6)} for r in records]
+
+
 def system_privacy_row(raw_upload_mb, fed_comm_mb):
     """run_federated.py:356-360."""
     has_raw = raw_upload_mb is not None
@@ -330,22 +358,30 @@ def main(argv=None):
             client_loaders.append({"loader": loader, "update_fn": update_fn})
 
         dp = fed["dp"]
-        dp_args = {}
+        round_args = {}
         if bool(dp["enabled"]):        # off: the call below is exactly the plain one
-            dp_args["dp"] = {"clip_norm": float(dp["clip_norm"]), "noise_multiplier": float(dp["noise_multiplier"]),
+            round_args["dp"] = {"clip_norm": float(dp["clip_norm"]), "noise_multiplier": float(dp["noise_multiplier"]),
                              "seed": seed if dp["seed"] is None else int(dp["seed"])}
-            log(f"[INFO] DP-FedAvg: clip_norm={dp_args['dp']['clip_norm']} "
-                f"noise_multiplier={dp_args['dp']['noise_multiplier']} delta={float(dp['delta'])}")
+            log(f"[INFO] DP-FedAvg: clip_norm={round_args['dp']['clip_norm']} "
+                f"noise_multiplier={round_args['dp']['noise_multiplier']} delta={float(dp['delta'])}")
+        comp = fed["compress"]
+        if bool(comp["enabled"]):      # off: the call below is exactly the plain one
+            round_args["compress"] = {"method": comp["method"], "error_feedback": bool(comp["error_feedback"])}
+            log(f"[INFO] Compressed uploads: method={comp['method']} error_feedback={bool(comp['error_feedback'])}")
         records = EXCHANGES[fed["exchange"]](
             global_model, client_models, client_loaders, client_sizes, lambda m: evaluate_topk(m, val_loader, device),
             device, rounds=int(fed["rounds"]), client_fraction=float(fed["client_fraction"]),
-            amp=bool(cfg["runtime"]["amp"]), log_f=log_f, **dp_args)
+            amp=bool(cfg["runtime"]["amp"]), log_f=log_f, **round_args)
 
         rows, comm_total = fed_summary_rows(records)
         fed_csv = out_dir / "fed_summary.csv"
         _write_csv(fed_csv, FED_COLUMNS, rows)
         log(f"[INFO] Saved federated summary: {fed_csv}")
-        if dp_args:
+        if "compress" in round_args:
+            comp_csv = out_dir / "fed_compress_summary.csv"
+            _write_csv(comp_csv, COMPRESS_COLUMNS, compress_summary_rows(records))
+            log(f"[INFO] Saved compression summary: {comp_csv}")
+        if "dp" in round_args:
             dp_csv = out_dir / "fed_dp_summary.csv"
             _write_csv(dp_csv, DP_COLUMNS, dp_summary_rows(records, dp, num_clients))
             log(f"[INFO] Saved DP summary (epsilon_est is an estimate): {dp_csv}")
