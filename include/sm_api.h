@@ -787,6 +787,51 @@ int sm_frames_resize_normalize(const uint8_t* packed, const int64_t* desc, int64
  * [blocks * 256] fp32 receives the accumulators.  Returns 0 or -2 (unknown shape). */
 int sm_calibrate_mfma(int shape, int iters, int blocks, int64_t* stamps, float* sink, hipStream_t st);
 
+/* ---- weighted k-nearest-neighbour evaluation of frozen features (Wu et al. 2018; csrc/knn.hip;
+ * no counterpart in the reference).  All fp32, rows contiguous, every pointer 4-byte aligned
+ * (else -2); no atomics, no host sync.
+ *
+ * sm_row_rnorm: x [N][D] -> rn [N], rn_i = ss_i > 0 ? 1.0f / sqrtf(ss_i) : 0 (a zero row has
+ * similarity 0 to everything, not NaN).  ss_i: 64 partial sums p_l = sum of x_id^2 over d = l,
+ * l + 64, ... ascending, one fmaf each, then five pairwise rounds p_l += p_(l xor o), o = 32, 16,
+ * 8, 4, 2, 1.
+ *
+ * sm_knn_topk: queries q [Nq][D], bank b [Nb][D] -> idx int32 [Nq][k], sim [Nq][k]: row i holds
+ * the first k bank rows under the total order below, with their similarities.
+ *   similarity  dot_ij = the fmaf chain acc = fmaf(q_id, b_jd, acc) from acc = +0 over d = 0, 1,
+ *               ..., D - 1 and on through zero products up to the next multiple of 32 (the
+ *               single-accumulator K loop of v_mfma_f32_32x32x2_f32): one order per pair, whatever
+ *               the tile, the partition or the load form.  rq [Nq] and rb [Nb] both given:
+ *               sim_ij = fl(fl(dot_ij * rq_i) * rb_j) (cosine, with sm_row_rnorm's vectors); both
+ *               null: sim_ij = dot_ij; exactly one null: -2.
+ *   order       larger sim first; equal sims (-0 == +0) by lower bank index; NaN after every
+ *               number, NaNs among themselves by index (the rule of sm_topk_frames and
+ *               sm_logits_metrics).  -inf is an ordinary value.
+ *   leave-one-out  self_offset >= 0 removes bank row i + self_offset from query i's candidates.
+ *   padding     with fewer than k candidates the remaining slots are idx = -1, sim = -inf.
+ *   splits      the bank is searched in `splits` partitions of ceil(Nb / splits) consecutive rows
+ *               by different blocks (0 = chosen from Nq and Nb; at most 1024), the partial lists
+ *               go to the workspace and a second launch merges them.  The order is total and
+ *               every sim has one summation order: the outputs are the same bits for every splits.
+ * 1 <= k <= 64, D >= 1, 1 <= Nq, Nb <= 2^31 - 256, else -2.  16-byte loads when D % 4 == 0 and
+ * q and b are 16-byte aligned, scalar loads otherwise (same bits).  Workspace
+ * sm_knn_topk_workspace_bytes(Nq, Nb, k, splits) (0 when one partition is searched), 16-byte
+ * aligned (else -4).
+ *
+ * sm_knn_vote: idx, sim [Nq][k], labels int64 [Nb], ks a HOST array of nk <= SM_KNN_MAX_KS
+ * strictly ascending values in [1, k] (else -2) -> scores [nk][Nq][C],
+ *   scores[s][i][c] = sum over r < ks[s] with labels[idx_ir] == c of expf(sim_ir * inv_temperature),
+ * added in rank order r ascending in fp32 (the table of ks[s] is a prefix of that of ks[s + 1]).
+ * A slot with idx outside [0, Nb), a label outside [0, C) or a NaN sim adds nothing.  C <=
+ * SM_LOGITS_MAX_CLASSES.  [nk * Nq][C] is the [S * N][C] layout sm_logits_metrics takes with S = nk. */
+#define SM_KNN_MAX_KS 8
+int sm_row_rnorm(const float* x, int64_t N, int D, float* rn, hipStream_t st);
+int64_t sm_knn_topk_workspace_bytes(int64_t Nq, int64_t Nb, int k, int splits);
+int sm_knn_topk(const float* q, int64_t Nq, const float* b, int64_t Nb, int D, const float* rq, const float* rb, int k,
+                int64_t self_offset, int splits, int32_t* idx, float* sim, void* ws, int64_t ws_bytes, hipStream_t st);
+int sm_knn_vote(const int32_t* idx, const float* sim, int64_t Nq, int k, const int64_t* labels, int64_t Nb, int C,
+                float inv_temperature, const int32_t* ks, int nk, float* scores, hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

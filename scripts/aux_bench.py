@@ -28,6 +28,10 @@
   and the eager q8_aggregate_reference in the same process, with the launch's bandwidth (see
   `fed_q8`).
 
+* `aux_bench.py knn [--out profiles/knn.txt]`: the kNN evaluation (knn.knn_eval: fused search,
+  vote, metrics) against the eager knn_reference in the same process at UCF101's list sizes and
+  at 16384 x 262144, and the search's achieved fp32 FLOP/s (see `knn`).
+
 Prints one JSON line per kernel; run under rocprofv3 --kernel-trace --stats to
 cross-check the average launch durations."""
 import json
@@ -643,10 +647,80 @@ def finetune(out_path=None, reps=10, rounds=7, num_classes=101):
     print(write(), end="")
 
 
+def knn(out_path=None, rounds=5, D=576, num_classes=101, temperature=0.07):
+    """The kNN evaluation (knn.knn_eval: two row-norm launches, the fused search, the vote and the
+    metrics launch, one readback) against knn.knn_reference (eager mm, stable sort, scatter_add,
+    chunked over the queries) on the same device in the same process, alternating, at k = 20,
+    ks = [1, 5, 10, 20], cosine, standard-normal features: Nq = 3783 / Nb = 9537 (UCF101 split 1's
+    test and train lists) and Nq = 16384 / Nb = 262144 (the eager path has to chunk).  The search
+    alone (sm_knn_topk with its merge launch, norm vectors given) is event-timed too, its
+    2 Nq Nb D FLOPs over that time next to the 157.3 TF fp32-matrix specification (a specification,
+    not a measurement on this device); at the small shape also with splits = 1 against auto.  The
+    two paths' idx are compared once per shape (a similarity is an fp32 sum in two different
+    orders there, so a few near-tied neighbours may swap).  Ends with the 4.9 GB copy calibration.
+    No speed-up is asserted: what is measured is written down."""
+    import statistics
+    from ssl_mae_amd import knn as KNN
+    ks, k = [1, 5, 10, 20], 20
+    lines = [f"device: {torch.cuda.get_device_name(0)}; D={D}, k={k}, ks={ks}, cosine, T={temperature}, "
+             f"{num_classes} classes; {rounds} rounds, median [min .. max]"]
+    for Nq, Nb, reps, ref_reps in ((3783, 9537, 20, 3), (16384, 262144, 2, 1)):
+        g = torch.Generator(device="cuda").manual_seed(Nq)
+        zq = torch.randn(Nq, D, device="cuda", generator=g)
+        zb = torch.randn(Nb, D, device="cuda", generator=g)
+        yq = torch.randint(0, num_classes, (Nq,), device="cuda", generator=g)
+        yb = torch.randint(0, num_classes, (Nb,), device="cuda", generator=g)
+        rq, rb = K.row_rnorm(zq), K.row_rnorm(zb)
+        auto = max(1, K.query("sm_knn_topk_workspace_bytes", Nq, Nb, k, 0) // (Nq * k * 8))
+
+        def fused():
+            return KNN.knn_eval(zq, yq, zb, yb, ks, temperature, num_classes)
+
+        def reference():
+            return KNN.knn_reference(zq, yq, zb, yb, ks, temperature, num_classes)
+
+        def search(splits=0):
+            return K.knn_topk(zq, zb, rq, rb, k, -1, splits)
+
+        a, b = fused(), reference()                     # warm-up of both paths, and the comparison
+        search()
+        search(1)
+        torch.cuda.synchronize()
+        same = (a["idx"] == b["idx"]).all(1).float().mean().item()
+        tf, tr, ts, t1 = [], [], [], []
+        for _ in range(rounds):                         # alternate the paths
+            tf += _rounds(fused, reps, 1)
+            tr += _rounds(reference, ref_reps, 1)
+            ts += _rounds(search, reps, 1)
+            if Nb < 100000:
+                t1 += _rounds(lambda: search(1), reps, 1)
+        mf, mr, ms = statistics.median(tf), statistics.median(tr), statistics.median(ts)
+        flop = 2.0 * Nq * Nb * D
+        lines.append(f"Nq={Nq} Nb={Nb} ({flop / 1e9:.1f} GFLOP of similarities, auto splits = {auto}):")
+        lines.append(f"  knn_eval fused (norms + search + vote + metrics + readback): {_fmt(tf)}")
+        lines.append(f"  knn_reference (eager torch, same device): {_fmt(tr)}  {mr / mf:.2f}x the fused path's time")
+        lines.append(f"  sm_knn_topk alone (auto splits): {_fmt(ts)}  {flop / ms / 1e9:.1f} TFLOP/s fp32, "
+                     f"{flop / ms / 1e9 / 157.3:.3f} of the 157.3 TF fp32-matrix specification")
+        if t1:
+            lines.append(f"  sm_knn_topk alone (splits = 1): {_fmt(t1)}  {statistics.median(t1) / ms:.2f}x auto")
+        lines.append(f"  rows with identical idx in both paths: {same:.4f}; top1 fused {a['top1']} reference {b['top1']}")
+        lines.append(f"  fused is {'FASTER' if mf < mr else 'NOT faster'} than the eager reference here")
+        del zq, zb, rq, rb, a, b
+        torch.cuda.empty_cache()
+    lines.append(_copy_calibration(rounds)[0])
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] in ("resize", "fedround", "finetune", "fed_dp", "fed_q8"):
+    if len(sys.argv) > 1 and sys.argv[1] in ("resize", "fedround", "finetune", "fed_dp", "fed_q8", "knn"):
         out = sys.argv[3] if len(sys.argv) > 3 and sys.argv[2] == "--out" else None
-        {"resize": resize, "fedround": fedround, "finetune": finetune, "fed_dp": fed_dp, "fed_q8": fed_q8}[sys.argv[1]](out)
+        {"resize": resize, "fedround": fedround, "finetune": finetune, "fed_dp": fed_dp, "fed_q8": fed_q8,
+         "knn": knn}[sys.argv[1]](out)
     else:
         main()
         frames()

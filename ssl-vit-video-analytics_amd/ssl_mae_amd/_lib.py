@@ -185,6 +185,11 @@ _SIGS = {
     "sm_grad_clip": (_c_i32, [_c_p, _c_p, _c_p, _c_i32, _c_f32, _c_p, _c_p, _c_i64, _c_p]),
     "sm_relu_dropout_fwd": (_c_i32, [_c_i32, _c_i64, _c_i32, _c_p, _c_p, _c_f32, _c_u64, _c_p]),
     "sm_relu_dropout_bwd": (_c_i32, [_c_i32, _c_i64, _c_i32, _c_p, _c_p, _c_p, _c_f32, _c_u64, _c_p]),
+    "sm_row_rnorm": (_c_i32, [_c_p, _c_i64, _c_i32, _c_p, _c_p]),
+    "sm_knn_topk_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i32, _c_i32]),
+    "sm_knn_topk": (_c_i32, [_c_p, _c_i64, _c_p, _c_i64, _c_i32, _c_p, _c_p, _c_i32, _c_i64, _c_i32, _c_p, _c_p, _c_p,
+                             _c_i64, _c_p]),
+    "sm_knn_vote": (_c_i32, [_c_p, _c_p, _c_i64, _c_i32, _c_p, _c_i64, _c_i32, _c_f32, _c_p, _c_i32, _c_p, _c_p]),
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-"""What the drivers (temporal_ssl, train_finetune, run_dynamic, run_privacy, run_federated) share:
+"""What the drivers (temporal_ssl, train_finetune, run_dynamic, run_privacy, run_federated, run_knn) share:
 the config merge, start-up, the classifier they all build, the synthetic and split-file clip
 sources, and the supervised pass and top-k evaluation of the two training drivers.  No driver
 imports another; they meet here and in the library modules (the log line and the CSV writer are

@@ -1600,3 +1600,78 @@ def relu_dropout_bwd(ref, dy, drop_p=0.0, seed=0):
     call("sm_relu_dropout_bwd", dt(ref), ref.numel(), ref.shape[-1], ptr(ref), ptr(dy), ptr(dx), float(drop_p),
          int(seed) & ((1 << 64) - 1), stream())
     return dx
+
+
+# ------------------------------------------------------------------ kNN evaluation
+KNN_MAX_K = 64     # one list entry per lane
+KNN_MAX_KS = 8     # SM_KNN_MAX_KS
+
+
+def _f32_rows(t, what):
+    """fp32 [N, D] device rows, contiguous (a view at any 4-byte offset is fine)."""
+    _chk(t)
+    if t.dim() != 2 or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() == 0:
+        raise _lib.KernelError(f"{what} must be a non-empty contiguous fp32 matrix")
+
+
+def row_rnorm(x):
+    """x fp32 [N,D] -> fp32 [N]: 1 / sqrt(sum_d x^2) in sm_row_rnorm's summation order, 0 for a zero row."""
+    _f32_rows(x, "row_rnorm: x")
+    N, D = x.shape
+    rn = torch.empty(N, dtype=torch.float32, device=x.device)
+    call("sm_row_rnorm", ptr(x), N, D, ptr(rn), stream())
+    return rn
+
+
+def knn_topk(q, bank, rq, rb, k, self_offset=-1, splits=0):
+    """q fp32 [Nq,D], bank fp32 [Nb,D], rq [Nq] / rb [Nb] (both or neither) -> (idx int32 [Nq,k],
+    sim fp32 [Nq,k]): each query's first k bank rows under sm_knn_topk's total order, slots past
+    the candidates idx = -1 / sim = -inf.  self_offset >= 0 drops bank row i + self_offset for
+    query i; splits bank partitions (0 = auto), the result the same bits for every value."""
+    _f32_rows(q, "knn_topk: q")
+    _f32_rows(bank, "knn_topk: bank")
+    _chk(rq, rb)
+    (Nq, D), Nb = q.shape, bank.shape[0]
+    if bank.shape[1] != D or bank.device != q.device:
+        raise _lib.KernelError("knn_topk: q and bank must share the feature width and the device")
+    if (rq is None) != (rb is None):
+        raise _lib.KernelError("knn_topk: give both norm vectors (cosine) or neither (dot)")
+    for t, n, what in ((rq, Nq, "rq"), (rb, Nb, "rb")):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (n,) or not t.is_contiguous()):
+            raise _lib.KernelError(f"knn_topk: {what} must be contiguous fp32 [{n}]")
+    k, splits = int(k), int(splits)
+    if not 1 <= k <= KNN_MAX_K:
+        raise _lib.KernelError(f"knn_topk: k must be in [1, {KNN_MAX_K}]")
+    idx = torch.empty((Nq, k), dtype=torch.int32, device=q.device)
+    sim = torch.empty((Nq, k), dtype=torch.float32, device=q.device)
+    nbytes = query("sm_knn_topk_workspace_bytes", Nq, Nb, k, splits)
+    ws = _ws(nbytes, q.device)
+    call("sm_knn_topk", ptr(q), Nq, ptr(bank), Nb, D, ptr(rq), ptr(rb), k, int(self_offset), splits, ptr(idx),
+         ptr(sim), ptr(ws), nbytes, stream())
+    return idx, sim
+
+
+def knn_vote(idx, sim, labels, num_classes, inv_temperature, ks):
+    """idx int32 / sim fp32 [Nq,k], labels int64 [Nb] -> scores fp32 [len(ks), Nq, C]: the
+    exp(sim * inv_temperature) weights of the first ks[s] neighbours added per class in rank
+    order (sm_knn_vote).  ks strictly ascending within [1, k]."""
+    import ctypes
+    _chk(idx, sim, labels)
+    if idx.dim() != 2 or idx.dtype != torch.int32 or not idx.is_contiguous() or idx.numel() == 0:
+        raise _lib.KernelError("knn_vote: idx must be a non-empty contiguous int32 matrix")
+    if sim.dtype != torch.float32 or sim.shape != idx.shape or not sim.is_contiguous():
+        raise _lib.KernelError("knn_vote: sim must match idx (contiguous fp32)")
+    if labels.dtype != torch.int64 or labels.dim() != 1 or not labels.is_contiguous() or labels.numel() == 0:
+        raise _lib.KernelError("knn_vote: labels must be a non-empty contiguous int64 vector")
+    ks = [int(v) for v in ks]
+    Nq, k = idx.shape
+    C = int(num_classes)
+    if not 1 <= len(ks) <= KNN_MAX_KS or ks[0] < 1 or ks[-1] > k or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise _lib.KernelError(f"knn_vote: ks must be 1..{KNN_MAX_KS} strictly ascending values within [1, {k}]")
+    if not 1 <= C <= LOGITS_MAX_CLASSES:
+        raise _lib.KernelError(f"knn_vote: num_classes must be in [1, {LOGITS_MAX_CLASSES}]")
+    scores = torch.empty((len(ks), Nq, C), dtype=torch.float32, device=idx.device)
+    arr = (ctypes.c_int32 * len(ks))(*ks)
+    call("sm_knn_vote", ptr(idx), ptr(sim), Nq, k, ptr(labels), labels.numel(), C, float(inv_temperature),
+         ctypes.cast(arr, ctypes.c_void_p), len(ks), ptr(scores), stream())
+    return scores

@@ -1663,6 +1663,47 @@ def relu_dropout_bwd(ref, dy, drop_p=0.0, seed=0):
     return torch.ops.ssl_mae.relu_dropout_bwd(ref, dy, float(drop_p), _s64(seed))
 
 
+# ============================================================================ kNN evaluation
+@_op("row_rnorm", "(Tensor x) -> Tensor")
+def _row_rnorm(x):
+    return _K.row_rnorm(x)
+
+
+_row_rnorm.register_fake(lambda x: x.new_empty((x.shape[0],), dtype=torch.float32))
+
+
+def row_rnorm(x):
+    return torch.ops.ssl_mae.row_rnorm(x)
+
+
+@_op("knn_topk", "(Tensor q, Tensor bank, Tensor? rq, Tensor? rb, int k, int self_offset, int splits) "
+                 "-> (Tensor, Tensor)")
+def _knn_topk(q, bank, rq, rb, k, self_offset, splits):
+    return _K.knn_topk(q, bank, rq, rb, k, self_offset, splits)
+
+
+_knn_topk.register_fake(lambda q, bank, rq, rb, k, self_offset, splits: (
+    q.new_empty((q.shape[0], k), dtype=torch.int32), q.new_empty((q.shape[0], k), dtype=torch.float32)))
+
+
+def knn_topk(q, bank, rq, rb, k, self_offset=-1, splits=0):
+    return torch.ops.ssl_mae.knn_topk(q, bank, rq, rb, int(k), int(self_offset), int(splits))
+
+
+@_op("knn_vote", "(Tensor idx, Tensor sim, Tensor labels, int num_classes, float inv_temperature, int[] ks) -> Tensor")
+def _knn_vote(idx, sim, labels, num_classes, inv_temperature, ks):
+    return _K.knn_vote(idx, sim, labels, num_classes, inv_temperature, ks)
+
+
+_knn_vote.register_fake(lambda idx, sim, labels, num_classes, inv_temperature, ks: sim.new_empty(
+    (len(ks), idx.shape[0], num_classes)))
+
+
+def knn_vote(idx, sim, labels, num_classes, inv_temperature, ks):
+    return torch.ops.ssl_mae.knn_vote(idx, sim, labels, int(num_classes), float(inv_temperature),
+                                      [int(v) for v in ks])
+
+
 def registered_ops():
     """Names of every ssl_mae operator registered by this module."""
     return sorted(n for n in dir(torch.ops.ssl_mae) if not n.startswith("_") and
