@@ -780,6 +780,19 @@ int sm_frames_resize_normalize(const uint8_t* packed, const int64_t* desc, int64
                                int Wo, const float* mean3, const float* std3, int bgr_swap, float* out,
                                hipStream_t st);
 
+/* The same launch with a source window per clip (random-resized crop): desc int64 [B][8] =
+ * {byte offset, Hs, Ws, flags, y0, x0, Hc, Wc}; clip b is still [T][Hs][Ws][3] in `packed`.  The
+ * result equals, bit for bit, sm_frames_resize_normalize applied to a buffer that holds only
+ * rows [y0, y0 + Hc) x columns [x0, x0 + Wc) of every frame: each axis runs with n_in = Hc
+ * (resp. Wc), so i1 = i0 + (i0 < Hc - 1) clamps at the window's edge and no pixel outside the
+ * window contributes, and y0 / x0 are added to i0 and i1.  The flip is within the window.  The
+ * window (0, 0, Hs, Ws) gives the bits of sm_frames_resize_normalize.  A clip is written as zeros
+ * under every rule above and also when y0 < 0, x0 < 0, Hc < 1, Wc < 1, y0 + Hc > Hs or
+ * x0 + Wc > Ws; nothing outside `packed` is read.  Arguments and return values as above. */
+int sm_frames_crop_resize_normalize(const uint8_t* packed, const int64_t* desc, int64_t packed_bytes, int B, int T,
+                                    int Ho, int Wo, const float* mean3, const float* std3, int bgr_swap, float* out,
+                                    hipStream_t st);
+
 /* ---- box calibration (bench.py; csrc/calib.hip): `blocks` workgroups of 4 waves, each wave
  * `iters` x 8 v_mfma_f32_32x32x16_bf16 (shape 32) or the same FLOPs as 16
  * v_mfma_f32_16x16x32_bf16 (shape 16) on random register operands.  stamps [blocks][2] int64:

@@ -32,6 +32,11 @@
   vote, metrics) against the eager knn_reference in the same process at UCF101's list sizes and
   at 16384 x 262144, and the search's achieved fp32 FLOP/s (see `knn`).
 
+* `aux_bench.py crop [--out profiles/crop_resize.txt]`: the random-resized-crop launch
+  (sm_frames_crop_resize_normalize) at the `resize` shapes with windows from the default sampler,
+  against sm_frames_resize_normalize on the full frames and against the same crop in eager torch
+  ops, alternating, and the 4.9 GB copy calibration (see `crop`).
+
 Prints one JSON line per kernel; run under rocprofv3 --kernel-trace --stats to
 cross-check the average launch durations."""
 import json
@@ -224,6 +229,89 @@ def resize(out_path=None, B=256, T=8, reps=20, rounds=5, host_threads=16):
         os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
         with open(out_path, "w") as f:
             f.write(text)
+
+
+def crop(out_path=None, B=256, T=8, reps=20, rounds=5, seed=0):
+    """sm_frames_crop_resize_normalize at the `resize` benchmark's shapes (112^2 -> 224^2 and
+    240x320 -> 112^2) with one window and flip per clip from mae_loader.RandomResizedCropFlip's
+    defaults at a fixed seed, alternating in every round with sm_frames_resize_normalize on the
+    full frames at the same output size (same bytes written, no fewer read) and with the same
+    crop in eager torch ops on the device (per clip: slice, float, div, interpolate, flip,
+    normalize, permute).  The crop's ratio to the full-frame launch stands beside that launch's own
+    spread over the rounds, (max - min) / median.  Algorithmic bytes of the crop: every byte of the
+    windows once + 12 per output pixel.  Ends with the 4.9 GB copy calibration."""
+    import statistics
+    import torch.nn.functional as Fn
+    from ssl_mae_amd.mae_loader import RandomResizedCropFlip
+    dev = torch.device("cuda")
+    lines = [f"device: {torch.cuda.get_device_name(0)}; B={B} T={T}; windows: RandomResizedCropFlip(seed={seed}) "
+             f"defaults; {rounds} rounds of {reps} launches, alternating, median [min .. max]"]
+    mean_t = torch.tensor(MEAN, device=dev).view(1, 3, 1, 1)
+    std_t = torch.tensor(STD, device=dev).view(1, 3, 1, 1)
+    for hs, ws, S in ((112, 112, 224), (240, 320, 112)):
+        src = torch.randint(0, 256, (B, T, hs, ws, 3), dtype=torch.uint8, device=dev)
+        desc4 = torch.tensor([[b * T * hs * ws * 3, hs, ws, 0] for b in range(B)])
+        aug = RandomResizedCropFlip(seed=seed)
+        desc8_host = aug.windows(desc4)
+        wins = desc8_host[:, 3:].tolist()
+        desc8 = desc8_host.to(dev)
+        desc4 = desc8[:, :4].contiguous()               # the same flips on the full frames
+        out = torch.empty((B, 3, T, S, S), dtype=torch.float32, device=dev)
+        out2 = torch.empty_like(out)
+        packed = src.view(-1)
+
+        def k_crop():
+            K.frames_crop_resize_normalize(packed, desc8, T, (S, S), MEAN, STD, False, out)
+
+        def k_full():
+            K.frames_resize_normalize(packed, desc4, T, (S, S), MEAN, STD, False, out2)
+
+        def eager():
+            clips = []
+            for b, (fl, y0, x0, hc, wc) in enumerate(wins):
+                x = src[b, :, y0:y0 + hc, x0:x0 + wc].permute(0, 3, 1, 2).float().div_(255.0)
+                x = Fn.interpolate(x, size=(S, S), mode="bilinear", align_corners=False)
+                if fl & 1:
+                    x = x.flip(3)
+                clips.append(((x - mean_t) / std_t).permute(1, 0, 2, 3))
+            return torch.stack(clips)
+
+        for fn in (k_crop, k_full, eager):              # warm-up: code objects, allocator
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        diff = float((eager() - out).abs().max())
+        tc, tf, te = [], [], []
+        for _ in range(rounds):                         # alternate the three paths
+            tc += _rounds(k_crop, reps, 1)
+            tf += _rounds(k_full, reps, 1)
+            te += _rounds(eager, 2, 1)
+        win_px = sum(hc * wc for _, _, _, hc, wc in wins)
+        gb_c = (T * win_px * 3 + out.numel() * 4) / 1e9
+        gb_f = (src.numel() + out.numel() * 4) / 1e9
+        mc, mf, me = statistics.median(tc), statistics.median(tf), statistics.median(te)
+        spread = (max(tf) - min(tf)) / mf
+        lines.append(f"{hs}x{ws} -> {S}x{S}: mean window {win_px / B / (hs * ws):.3f} of the frame, "
+                     f"{sum(fl & 1 for fl, *_ in wins)} of {B} clips flipped, {sum(aug.last_fallback)} fallbacks")
+        lines.append(f"  sm_frames_crop_resize_normalize: {_fmt(tc)}  {gb_c:.3f} GB per launch  {gb_c / mc * 1e3:.0f} GB/s")
+        lines.append(f"  sm_frames_resize_normalize, full frames: {_fmt(tf)}  {gb_f:.3f} GB per launch  "
+                     f"{gb_f / mf * 1e3:.0f} GB/s")
+        lines.append(f"  crop / full-frame time: {mc / mf:.3f}; the full-frame launch's own spread over the rounds, "
+                     f"(max - min) / median: {spread:.3f}")
+        lines.append(f"  eager torch ops on the GPU (per clip: slice, float, div, interpolate, flip, normalize, permute; "
+                     f"stack): {_fmt(te)}  {me / mc:.1f}x the kernel; max |eager - kernel| = {diff:.2e}")
+        lines.append(f"  the fused launch is {'FASTER' if mc < me else 'NOT faster'} than the eager path here")
+        del src, out, out2, packed
+        torch.cuda.empty_cache()
+    lines.append(_copy_calibration(rounds)[0])
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+    if "NOT faster" in text:
+        raise SystemExit("the fused crop launch is not faster than the eager path")
 
 
 def fedround(out_path=None, reps=5, rounds=5, num_classes=101):
@@ -717,9 +805,9 @@ def knn(out_path=None, rounds=5, D=576, num_classes=101, temperature=0.07):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] in ("resize", "fedround", "finetune", "fed_dp", "fed_q8", "knn"):
+    if len(sys.argv) > 1 and sys.argv[1] in ("resize", "crop", "fedround", "finetune", "fed_dp", "fed_q8", "knn"):
         out = sys.argv[3] if len(sys.argv) > 3 and sys.argv[2] == "--out" else None
-        {"resize": resize, "fedround": fedround, "finetune": finetune, "fed_dp": fed_dp, "fed_q8": fed_q8,
+        {"resize": resize, "crop": crop, "fedround": fedround, "finetune": finetune, "fed_dp": fed_dp, "fed_q8": fed_q8,
          "knn": knn}[sys.argv[1]](out)
     else:
         main()

@@ -28,17 +28,26 @@
 // [1, 8192], or when its byte range leaves [0, packed_bytes): nothing outside
 // `packed` is ever read.
 //
+// sm_frames_crop_resize_normalize is the same kernel body with a source window per clip
+// (desc int64 [B][8] = {byte offset, Hs, Ws, flags, y0, x0, Hc, Wc}): the result is, bit for
+// bit, the above applied to a buffer that holds only rows [y0, y0 + Hc) x columns
+// [x0, x0 + Wc) of every frame.  Each axis runs over the window (n_in = Hc resp. Wc, so the
+// edge clamp is the window's edge and no pixel outside it contributes) and y0 / x0 enter
+// only the byte address of the window's first pixel; the flip is within the window.  A window
+// that leaves its frame, or has Hc < 1 or Wc < 1, also gives a zero clip.  The full frame is
+// the window (0, 0, Hs, Ws), which is what the 4-column instantiation fixes at compile time.
+//
 // Output-stationary and HBM-bound (12 B written, at most 12 B read per output pixel).
 // A block owns kRows output rows x kCols output columns of one frame.  It tabulates
 // u / 255 (256 values) and the per-column (x0, l1x) once in LDS, stages the source
 // rows the band touches into LDS with aligned dword loads, four in flight per lane (clip
 // offsets and Ws * 3 are arbitrary: the byte range is aligned down, the dwords that straddle
 // the ends of `packed` are assembled from in-range bytes; a tile as wide as the frame needs
-// one contiguous range, a narrower one a segment per row) and gathers from LDS.  A tile whose
-// source footprint exceeds kStage (very wide rows, extreme downscales) gathers from
-// global memory instead; same arithmetic, same bits.  One lane produces 4 consecutive
-// columns: a 16-B non-temporal store per channel plane when Wo % 4 == 0 and `out` is
-// 16-B aligned, scalar stores of the same elements otherwise.
+// one contiguous range (so does a full-width window), a narrower one a segment per row) and
+// gathers from LDS.  A tile whose source footprint exceeds kStage (very wide rows, extreme
+// downscales) gathers from global memory instead; same arithmetic, same bits.  One lane
+// produces 4 consecutive columns: a 16-B non-temporal store per channel plane when
+// Wo % 4 == 0 and `out` is 16-B aligned, scalar stores of the same elements otherwise.
 #include "common.h"
 #include "sm_api.h"
 
@@ -83,8 +92,9 @@ SM_DEV float lerp2(float l0x, float l1x, float l0y, float l1y, float p00, float 
   return l0y * top + l1y * bot;
 }
 
-// The rows [r0, r1) x columns [c0, c1) of one output frame.  row_ptr(y) yields the byte
-// pointer of source pixel xlo in source row y: LDS (staged) or global memory.
+// The rows [r0, r1) x columns [c0, c1) of one output frame.  Hs x Ws is the source window and
+// every source index is relative to it; row_ptr(y) yields the byte pointer of pixel xlo in
+// row y of the window: LDS (staged) or global memory.
 template <typename RowPtr>
 SM_DEV void produce(RowPtr row_ptr, const float* lut, const int* col_x0, const float* col_l1, int Hs, int Ws, int Ho,
                     int Wo, int r0, int r1, int c0, int c1, int xlo, const float* mean, const float* sd, int bgr,
@@ -125,6 +135,8 @@ SM_DEV void produce(RowPtr row_ptr, const float* lut, const int* col_x0, const f
   }
 }
 
+// kWin: desc rows carry a source window (8 columns); otherwise the window is the frame.
+template <bool kWin>
 __global__ void __launch_bounds__(256) resize_norm_kernel(const uint8_t* __restrict__ packed,
                                                          const int64_t* __restrict__ desc, int64_t packed_bytes,
                                                          int T, int Ho, int Wo, int bands, int ctiles, Norm nm,
@@ -144,10 +156,23 @@ __global__ void __launch_bounds__(256) resize_norm_kernel(const uint8_t* __restr
   const int64_t plane = (int64_t)T * Ho * Wo;           // one output channel of one clip
   float* out_frame = out + (int64_t)b * 3 * plane + (int64_t)t * Ho * Wo;
 
-  const int64_t off = desc[b * 4 + 0], hs64 = desc[b * 4 + 1], ws64 = desc[b * 4 + 2], flags = desc[b * 4 + 3];
+  constexpr int kDesc = kWin ? 8 : 4;
+  const int64_t* d = desc + (int64_t)b * kDesc;
+  const int64_t off = d[0], hs64 = d[1], ws64 = d[2], flags = d[3];
   bool ok = (flags & 2) == 0 && hs64 >= 1 && hs64 <= kMaxSrc && ws64 >= 1 && ws64 <= kMaxSrc && off >= 0 &&
             off <= packed_bytes;
   if (ok) ok = (int64_t)T * hs64 * ws64 * 3 <= packed_bytes - off;
+  int wy = 0, wx = 0;                                   // the window's origin in the frame
+  int64_t hc64 = hs64, wc64 = ws64;
+  if (kWin && ok) {                                     // (hs64, ws64 <= kMaxSrc: the sums cannot overflow)
+    const int64_t y064 = d[4], x064 = d[5];
+    hc64 = d[6];
+    wc64 = d[7];
+    ok = y064 >= 0 && x064 >= 0 && hc64 >= 1 && wc64 >= 1 && hc64 <= hs64 && wc64 <= ws64 &&
+         y064 <= hs64 - hc64 && x064 <= ws64 - wc64;
+    wy = (int)y064;
+    wx = (int)x064;
+  }
   if (!ok) {                                            // block-uniform: zero clip
     const int ng = (c1 - c0 + 3) >> 2, items = (r1 - r0) * ng;
     for (int it = threadIdx.x; it < items; it += blockDim.x) {
@@ -164,24 +189,27 @@ __global__ void __launch_bounds__(256) resize_norm_kernel(const uint8_t* __restr
     }
     return;
   }
-  const int Hs = (int)hs64, Ws = (int)ws64;
+  const int Ws = (int)ws64;                             // the frame's row pitch in pixels
+  const int Hc = (int)hc64, Wc = (int)wc64;             // the window (the frame when !kWin)
   const bool flip = (flags & 1) != 0;
 
   for (int i = threadIdx.x; i < 256; i += blockDim.x) lut[i] = (float)i / 255.0f;
   for (int i = threadIdx.x; i < c1 - c0; i += blockDim.x) {
     const int ox = c0 + i;
-    const Axis ax = axis_at(Ws, Wo, flip ? Wo - 1 - ox : ox);
+    const Axis ax = axis_at(Wc, Wo, flip ? Wo - 1 - ox : ox);
     col_x0[i] = ax.i0;
     col_l1[i] = ax.l1;
   }
-  // source footprint of the tile (i0 and i1 never decrease with the output index)
+  // source footprint of the tile, relative to the window (i0 and i1 never decrease with the
+  // output index)
   const int xa = flip ? Wo - c1 : c0, xb = flip ? Wo - 1 - c0 : c1 - 1;
-  const int xlo = axis_at(Ws, Wo, xa).i0, xhi = axis_at(Ws, Wo, xb).i1;
-  const int ylo = axis_at(Hs, Ho, r0).i0, yhi = axis_at(Hs, Ho, r1 - 1).i1;
+  const int xlo = axis_at(Wc, Wo, xa).i0, xhi = axis_at(Wc, Wo, xb).i1;
+  const int ylo = axis_at(Hc, Ho, r0).i0, yhi = axis_at(Hc, Ho, r1 - 1).i1;
   const int nrows = yhi - ylo + 1, seg = (xhi - xlo + 1) * 3;
-  // A tile that spans the source width needs one contiguous byte range (nrows whole rows):
-  // one segment, rows Ws * 3 bytes apart in LDS.  A narrower tile stages one segment per row,
-  // each aligned down on its own, `pitch` bytes apart (a segment plus its shift, whole dwords).
+  // A tile that spans the frame's width (so Wc == Ws) needs one contiguous byte range (nrows
+  // whole rows): one segment, rows Ws * 3 bytes apart in LDS.  A narrower tile or window stages
+  // one segment per row, each aligned down on its own, `pitch` bytes apart (a segment plus its
+  // shift, whole dwords).
   const bool whole = seg == Ws * 3;
   const int nseg = whole ? 1 : nrows, seg_bytes = whole ? nrows * seg : seg;
   const int pitch = whole ? seg : (seg + 6) & ~3;
@@ -193,40 +221,53 @@ __global__ void __launch_bounds__(256) resize_norm_kernel(const uint8_t* __restr
     mean[c] = bgr ? nm.mean[2 - c] : nm.mean[c];
     sd[c] = bgr ? nm.std[2 - c] : nm.std[c];
   }
-  // byte index in `packed` of pixel xlo of source row y of this frame
-  const int64_t frame_byte = off + (int64_t)t * Hs * Ws * 3 + (int64_t)xlo * 3;
+  // byte index in `packed` of pixel xlo of the window's row 0 in this frame; the window's row y
+  // is y * row_bytes further
+  const int64_t frame_byte = off + ((int64_t)t * hs64 * Ws + (int64_t)wy * Ws + wx + xlo) * 3;
   const int64_t row_bytes = (int64_t)Ws * 3;
 
   if (staged) {
     const uint8_t* end = packed + packed_bytes;
-    for (int r = 0; r < nseg; ++r) {
-      const uint8_t* g = packed + frame_byte + (ylo + r) * row_bytes;
-      const int shift = (int)((uintptr_t)g & 3u);
-      const uint8_t* a = g - shift;                     // aligned down
-      const int ndw = (shift + seg_bytes + 3) >> 2;     // whole: <= kStage / 4; else ndw * 4 <= pitch
-      uint32_t* dst = stage + (whole ? 0 : r * (pitch >> 2));
-      // kLoads independent loads per lane in flight, then their LDS stores
-      for (int i0 = threadIdx.x; i0 < ndw; i0 += kLoads * (int)blockDim.x) {
-        uint32_t w[kLoads];
+    const uint8_t* g0 = packed + frame_byte + ylo * row_bytes;        // pixel xlo of the first staged row
+    // Stage dword i is dword i % pdw of segment i / pdw, counted from that segment's aligned-down
+    // start.  whole has one segment.  Otherwise every row segment is in the same pass, pdw =
+    // pitch / 4 dwords each (a row's shift and segment fit: shift + seg + 3 <= pitch), so that
+    // short segments (a narrow window) fill the lanes together instead of paying one pass, and
+    // one memory latency, per row.  In all ndw * 4 <= kStage.
+    const int shift0 = (int)((uintptr_t)g0 & 3u);
+    const int pdw = whole ? (shift0 + seg_bytes + 3) >> 2 : pitch >> 2;
+    const int ndw = nseg * pdw;
+    // kLoads independent loads per lane in flight, then their LDS stores
+    for (int i0 = threadIdx.x; i0 < ndw; i0 += kLoads * (int)blockDim.x) {
+      uint32_t w[kLoads];
 #pragma unroll
-        for (int u = 0; u < kLoads; ++u) {
-          const int i = i0 + u * (int)blockDim.x;
-          const uint8_t* p = a + 4 * (int64_t)i;
-          w[u] = 0;
-          if (i < ndw) {
-            if (p >= packed && p + 4 <= end) {
-              w[u] = *(const uint32_t*)p;
-            } else {                                    // a dword across an end of `packed`
-              for (int k = 0; k < 4; ++k)
-                if (p + k >= packed && p + k < end) w[u] |= (uint32_t)p[k] << (8 * k);
-            }
+      for (int u = 0; u < kLoads; ++u) {
+        const int i = i0 + u * (int)blockDim.x;
+        // The address is formed in front of the guarded load, the division only behind the
+        // block-uniform !whole branch: this keeps the kLoads loads in flight.  For i >= ndw the
+        // pointer lies behind the staged rows and is never dereferenced.
+        const uint8_t* p;
+        if (whole) {
+          p = g0 - shift0 + 4 * (int64_t)i;
+        } else {
+          const int r = i / pdw;
+          const uint8_t* g = g0 + r * row_bytes;
+          p = g - ((uintptr_t)g & 3u) + 4 * (i - r * pdw);
+        }
+        w[u] = 0;
+        if (i < ndw) {
+          if (p >= packed && p + 4 <= end) {
+            w[u] = *(const uint32_t*)p;
+          } else {                                      // a dword across an end of `packed`
+            for (int k = 0; k < 4; ++k)
+              if (p + k >= packed && p + k < end) w[u] |= (uint32_t)p[k] << (8 * k);
           }
         }
+      }
 #pragma unroll
-        for (int u = 0; u < kLoads; ++u) {
-          const int i = i0 + u * (int)blockDim.x;
-          if (i < ndw) dst[i] = w[u];
-        }
+      for (int u = 0; u < kLoads; ++u) {
+        const int i = i0 + u * (int)blockDim.x;
+        if (i < ndw) stage[i] = w[u];
       }
     }
     __syncthreads();
@@ -237,21 +278,19 @@ __global__ void __launch_bounds__(256) resize_norm_kernel(const uint8_t* __restr
       const int shift = (int)(((uintptr_t)packed + (uint64_t)first) & 3u);
       return sbytes + (y - ylo) * pitch + shift;
     };
-    produce(row_ptr, lut, col_x0, col_l1, Hs, Ws, Ho, Wo, r0, r1, c0, c1, xlo, mean, sd, bgr,
+    produce(row_ptr, lut, col_x0, col_l1, Hc, Wc, Ho, Wo, r0, r1, c0, c1, xlo, mean, sd, bgr,
                             vec != 0, out_frame, plane);
   } else {
     __syncthreads();
     auto row_ptr = [&](int y) -> const uint8_t* { return packed + frame_byte + y * row_bytes; };
-    produce(row_ptr, lut, col_x0, col_l1, Hs, Ws, Ho, Wo, r0, r1, c0, c1, xlo, mean, sd, bgr,
+    produce(row_ptr, lut, col_x0, col_l1, Hc, Wc, Ho, Wo, r0, r1, c0, c1, xlo, mean, sd, bgr,
                             vec != 0, out_frame, plane);
   }
 }
 
-}  // namespace
-
-extern "C" int sm_frames_resize_normalize(const uint8_t* packed, const int64_t* desc, int64_t packed_bytes, int B,
-                                          int T, int Ho, int Wo, const float* mean3, const float* std3,
-                                          int bgr_swap, float* out, hipStream_t st) {
+template <bool kWin>
+int launch_resize(const uint8_t* packed, const int64_t* desc, int64_t packed_bytes, int B, int T, int Ho, int Wo,
+                  const float* mean3, const float* std3, int bgr_swap, float* out, hipStream_t st) {
   if (B < 0 || T < 0 || Ho < 0 || Wo < 0 || Ho > kMaxDst || Wo > kMaxDst || packed_bytes < 0) return -2;
   if ((int64_t)B * T * Ho * Wo == 0) return 0;
   if (!desc || !mean3 || !std3 || !out || (!packed && packed_bytes > 0)) return -2;   // (mean3 / std3: host arrays)
@@ -264,8 +303,22 @@ extern "C" int sm_frames_resize_normalize(const uint8_t* packed, const int64_t* 
     nm.std[c] = std3[c];
   }
   const int vec = Wo % 4 == 0 && ((uintptr_t)out & 15u) == 0;
-  hipLaunchKernelGGL(resize_norm_kernel, dim3((unsigned)blocks), dim3(256), 0, st, packed, desc, packed_bytes, T, Ho,
-                     Wo, bands, ctiles, nm, bgr_swap, vec, out);
+  hipLaunchKernelGGL(resize_norm_kernel<kWin>, dim3((unsigned)blocks), dim3(256), 0, st, packed, desc, packed_bytes,
+                     T, Ho, Wo, bands, ctiles, nm, bgr_swap, vec, out);
   SM_CHECK_LAUNCH();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int sm_frames_resize_normalize(const uint8_t* packed, const int64_t* desc, int64_t packed_bytes, int B,
+                                          int T, int Ho, int Wo, const float* mean3, const float* std3,
+                                          int bgr_swap, float* out, hipStream_t st) {
+  return launch_resize<false>(packed, desc, packed_bytes, B, T, Ho, Wo, mean3, std3, bgr_swap, out, st);
+}
+
+extern "C" int sm_frames_crop_resize_normalize(const uint8_t* packed, const int64_t* desc, int64_t packed_bytes,
+                                               int B, int T, int Ho, int Wo, const float* mean3, const float* std3,
+                                               int bgr_swap, float* out, hipStream_t st) {
+  return launch_resize<true>(packed, desc, packed_bytes, B, T, Ho, Wo, mean3, std3, bgr_swap, out, st);
 }

@@ -124,12 +124,14 @@ class ClipSetLoader:
 
 # ------------------------------------------------------------------ split files
 def split_file_loader(split, *, clip_len, stride, image_size, batch_size, num_workers, device, labelled=True,
-                      bgr_swap=True, shuffle=False, drop_last=False, seed=None, pin_memory=False):
+                      bgr_swap=True, shuffle=False, drop_last=False, seed=None, pin_memory=False, augment=None):
     """Clips of a split file (lines of `<frame directory> [<label>]`): frames decoded on the host
     at their own size, resized to `image_size` and normalised on the device
     (mae_loader.ClipResizer).  `labelled` yields (clip, label) with the label from the second
     column, otherwise the clip alone.  `shuffle` draws its order from a generator seeded with
-    `seed`, or from torch's global one when `seed` is None."""
+    `seed`, or from torch's global one when `seed` is None.  `augment` (a
+    mae_loader.RandomResizedCropFlip) gives every clip of a batch a source window and a flip
+    decision, drawn here in the main process after collation."""
     from .mae_loader import ClipResizer, LazyVideoMAEDataset, collate_raw
     data = LazyVideoMAEDataset(split, clip_len=int(clip_len), stride=int(stride), image_size=int(image_size))
     norm = ClipResizer(int(image_size), bgr_swap=bgr_swap, device=device)
@@ -160,6 +162,8 @@ def split_file_loader(split, *, clip_len, stride, image_size, batch_size, num_wo
 
         def __iter__(self):
             for packed, desc, *label in loader:
+                if augment is not None:
+                    desc = augment.windows(desc)
                 clip = norm(packed, desc, int(clip_len))
                 yield (clip, label[0].to(device)) if labelled else clip
 

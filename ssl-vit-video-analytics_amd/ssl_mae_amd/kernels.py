@@ -1239,24 +1239,20 @@ def frames_normalize(frames, mean, std, bgr_swap=True, valid=None, out=None):
     return out
 
 
-def frames_resize_normalize(packed, desc, T, out_hw, mean, std, bgr_swap=True, out=None):
-    """packed uint8 (1-D; clip b = [T,Hs_b,Ws_b,3] RGB at byte desc[b,0]) + desc int64 [B,4]
-    {byte offset, Hs, Ws, flags (1 = flip, 2 = invalid)} -> fp32 [B,3,T,Ho,Wo]: bilinear resize
-    (align_corners=False), clip-level horizontal flip and normalisation in one launch
-    (mae_dataset.py:84-90, :129-133).  A clip whose range leaves `packed`, or whose size is
-    outside [1, 8192], comes back as zeros."""
+def _frames_resize(symbol, cols, packed, desc, T, out_hw, mean, std, bgr_swap, out):
     import ctypes
+    name = symbol[3:]
     _chk(packed, desc)
     if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
         raise _lib.KernelError("packed must be a contiguous 1-D uint8 tensor")
-    if desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != 4 or not desc.is_contiguous():
-        raise _lib.KernelError("desc must be a contiguous int64 [B,4] tensor")
+    if desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != cols or not desc.is_contiguous():
+        raise _lib.KernelError(f"desc must be a contiguous int64 [B,{cols}] tensor")
     if desc.device != packed.device:
         raise _lib.KernelError("packed and desc must be on one device")
     B, T = desc.shape[0], int(T)
     Ho, Wo = (int(x) for x in out_hw)
     if T < 0 or not (0 <= Ho <= 4096 and 0 <= Wo <= 4096):
-        raise _lib.KernelError("frames_resize_normalize needs T >= 0 and an output size within [0, 4096]")
+        raise _lib.KernelError(f"{name} needs T >= 0 and an output size within [0, 4096]")
     if out is None:
         out = torch.empty((B, 3, T, Ho, Wo), dtype=torch.float32, device=packed.device)
     else:
@@ -1265,9 +1261,27 @@ def frames_resize_normalize(packed, desc, T, out_hw, mean, std, bgr_swap=True, o
             raise _lib.KernelError(f"out must be contiguous fp32 [{B},3,{T},{Ho},{Wo}]")
     m = (ctypes.c_float * 3)(*[float(x) for x in mean])
     s = (ctypes.c_float * 3)(*[float(x) for x in std])
-    call("sm_frames_resize_normalize", ptr(packed), ptr(desc), packed.numel(), B, T, Ho, Wo,
-         ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p), 1 if bgr_swap else 0, ptr(out), stream())
+    call(symbol, ptr(packed), ptr(desc), packed.numel(), B, T, Ho, Wo, ctypes.cast(m, ctypes.c_void_p),
+         ctypes.cast(s, ctypes.c_void_p), 1 if bgr_swap else 0, ptr(out), stream())
     return out
+
+
+def frames_resize_normalize(packed, desc, T, out_hw, mean, std, bgr_swap=True, out=None):
+    """packed uint8 (1-D; clip b = [T,Hs_b,Ws_b,3] RGB at byte desc[b,0]) + desc int64 [B,4]
+    {byte offset, Hs, Ws, flags (1 = flip, 2 = invalid)} -> fp32 [B,3,T,Ho,Wo]: bilinear resize
+    (align_corners=False), clip-level horizontal flip and normalisation in one launch
+    (mae_dataset.py:84-90, :129-133).  A clip whose range leaves `packed`, or whose size is
+    outside [1, 8192], comes back as zeros."""
+    return _frames_resize("sm_frames_resize_normalize", 4, packed, desc, T, out_hw, mean, std, bgr_swap, out)
+
+
+def frames_crop_resize_normalize(packed, desc, T, out_hw, mean, std, bgr_swap=True, out=None):
+    """frames_resize_normalize with a source window per clip: desc int64 [B,8] {byte offset, Hs,
+    Ws, flags, y0, x0, Hc, Wc}.  The output is rows [y0, y0 + Hc) x columns [x0, x0 + Wc) of every
+    frame resized to (Ho, Wo), bit for bit what frames_resize_normalize gives on a buffer that
+    holds only the window; the flip is within the window.  A window that leaves its frame or is
+    empty gives a zero clip, as every descriptor does that frames_resize_normalize rejects."""
+    return _frames_resize("sm_frames_crop_resize_normalize", 8, packed, desc, T, out_hw, mean, std, bgr_swap, out)
 
 
 # ------------------------------------------------------------------ streaming dynamic inference

@@ -22,6 +22,11 @@ a descriptor row {byte offset, Hs, Ws, flags} per clip, and sm_frames_resize_nor
 resizes (bilinear, align_corners=False, the rule of src/datasets/mae_dataset.py:84-90),
 flips and normalises every clip in one launch.  A clip already at `image_size` comes out
 bit-identical to the ClipNormalizer path, so the drivers use this path for every split.
+`RandomResizedCropFlip` turns that launch into the training augmentation: it draws one source
+window and one flip per clip on the host (every frame of a clip gets the same crop) and widens
+the descriptor to {byte offset, Hs, Ws, flags, y0, x0, Hc, Wc}, which ClipResizer hands to
+sm_frames_crop_resize_normalize: still one copy and one launch, the crop costs no pixel work on
+the host.  The reference has no augmentation (src/datasets/transforms.py).
 Deviation: the reference's supervised loaders resize with cv2.resize
 (src/datasets/transforms.py:9-15), whose bilinear filter works in fixed-point uint8
 arithmetic.  OpenCV is not available to pin that arithmetic against, so every loader here
@@ -44,6 +49,7 @@ noise row is replaced by distinct values in the order of the reference's own
 `torch.argsort(noise[b], descending=True)`.  The kernel's ranking then reproduces the
 reference's selection by construction.
 """
+import math
 import os
 
 import numpy as np
@@ -185,9 +191,84 @@ def collate_raw(batch):
     return packed, desc
 
 
+class RandomResizedCropFlip:
+    """Clip-consistent random-resized crop and horizontal flip for ClipResizer: `windows` maps
+    collate_raw's desc [B,4] to desc [B,8] = {byte offset, Hs, Ws, flags, y0, x0, Hc, Wc}, one
+    window and one flip decision per clip.  A pure host function of the descriptor and of this
+    object's own generator, called in the main process after collation, so a run does not depend
+    on num_workers.
+
+    The usual rule, per valid clip: up to TRIES tries of area = Hs * Ws * U(scale),
+    ar = exp(U(log ratio[0], log ratio[1])), w = round(sqrt(area * ar)), h = round(sqrt(area / ar));
+    the first try with 1 <= w <= Ws and 1 <= h <= Hs is taken and y0, x0 are uniform over the
+    positions that keep the window inside the frame.  When no try fits, the window is the centred
+    largest one whose aspect Ws / Hs is clamped to `ratio`.  FLAG_FLIP is set with probability
+    `flip`.  An invalid clip keeps its flags and gets a zero window.
+
+    Order of the draws: every call makes ONE draw, u = torch.rand(B, 2 * TRIES + 3, float64), from
+    the generator; row b belongs to clip b whether or not it is valid and whatever it accepts, so
+    the stream does not depend on the data.  u[b, 2 i] is try i's area, u[b, 2 i + 1] its aspect,
+    then come y0 (floor(u * (Hs - h + 1))), x0 (floor(u * (Ws - w + 1))) and the flip (u < flip).
+    `last_fallback` lists, for the last call, whether each clip took the fallback."""
+
+    TRIES = 10
+
+    def __init__(self, scale=(0.35, 1.0), ratio=(3 / 4, 4 / 3), flip=0.5, seed=0):
+        self.scale = (float(scale[0]), float(scale[1]))
+        self.ratio = (float(ratio[0]), float(ratio[1]))
+        self.flip = float(flip)
+        if not 0.0 < self.scale[0] <= self.scale[1] <= 1.0:
+            raise ValueError(f"RandomResizedCropFlip needs 0 < scale[0] <= scale[1] <= 1, got {scale}")
+        if not 0.0 < self.ratio[0] <= self.ratio[1]:
+            raise ValueError(f"RandomResizedCropFlip needs 0 < ratio[0] <= ratio[1], got {ratio}")
+        if not 0.0 <= self.flip <= 1.0:
+            raise ValueError(f"RandomResizedCropFlip needs flip within [0, 1], got {flip}")
+        self.gen = torch.Generator().manual_seed(int(seed))
+        self.last_fallback = []
+
+    def _fallback(self, hs, ws):
+        in_ratio = ws / hs
+        h, w = hs, ws
+        if in_ratio < self.ratio[0]:
+            h = min(hs, max(1, math.floor(ws / self.ratio[0] + 0.5)))
+        elif in_ratio > self.ratio[1]:
+            w = min(ws, max(1, math.floor(hs * self.ratio[1] + 0.5)))
+        return (hs - h) // 2, (ws - w) // 2, h, w
+
+    def windows(self, desc):
+        if desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != 4:
+            raise ValueError("RandomResizedCropFlip.windows takes an int64 [B,4] descriptor")
+        B = desc.shape[0]
+        u = torch.rand(B, 2 * self.TRIES + 3, dtype=torch.float64, generator=self.gen).tolist()
+        log_r = (math.log(self.ratio[0]), math.log(self.ratio[1]))
+        out = torch.zeros(B, 8, dtype=torch.int64)
+        out[:, :4] = desc
+        self.last_fallback = [False] * B
+        for b, (_, hs, ws, flags) in enumerate(desc.tolist()):
+            if flags & FLAG_INVALID or hs < 1 or ws < 1:
+                continue
+            ub, win = u[b], None
+            for i in range(self.TRIES):
+                area = hs * ws * (self.scale[0] + (self.scale[1] - self.scale[0]) * ub[2 * i])
+                ar = math.exp(log_r[0] + (log_r[1] - log_r[0]) * ub[2 * i + 1])
+                w, h = math.floor(math.sqrt(area * ar) + 0.5), math.floor(math.sqrt(area / ar) + 0.5)
+                if 1 <= w <= ws and 1 <= h <= hs:
+                    y0 = min(int(ub[2 * self.TRIES] * (hs - h + 1)), hs - h)
+                    x0 = min(int(ub[2 * self.TRIES + 1] * (ws - w + 1)), ws - w)
+                    win = (y0, x0, h, w)
+                    break
+            if win is None:
+                win, self.last_fallback[b] = self._fallback(hs, ws), True
+            out[b, 4:] = torch.tensor(win)
+            if ub[2 * self.TRIES + 2] < self.flip:
+                out[b, 3] = flags | FLAG_FLIP
+        return out
+
+
 class ClipResizer:
     """Packed host frames -> resized, flipped, normalised fp32 clip [B,3,T,S,S] in HBM: one
-    H2D copy of the pixels, one of the descriptors, one launch (sm_frames_resize_normalize)."""
+    H2D copy of the pixels, one of the descriptors, one launch (sm_frames_resize_normalize, or
+    sm_frames_crop_resize_normalize when the descriptor has a window: 8 columns)."""
 
     def __init__(self, image_size, mean=IMAGENET_MEAN, std=IMAGENET_STD, bgr_swap=True, device="cuda"):
         hw = (image_size, image_size) if isinstance(image_size, int) else tuple(image_size)
@@ -201,12 +282,12 @@ class ClipResizer:
         from ._lib import KernelError
         if packed.dtype != torch.uint8 or packed.dim() != 1:
             raise KernelError("packed must be a 1-D uint8 tensor")
-        if desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != 4:
-            raise KernelError("desc must be an int64 [B,4] tensor")
+        if desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] not in (4, 8):
+            raise KernelError("desc must be an int64 [B,4] or [B,8] tensor")
         if int(T) < 0:
             raise KernelError("the clip length must not be negative")
         n = packed.numel()
-        for b, (off, hs, ws, flags) in enumerate(desc.tolist()):
+        for b, (off, hs, ws, flags, *win) in enumerate(desc.tolist()):
             if flags & FLAG_INVALID:
                 continue
             if not (1 <= hs <= MAX_SOURCE_SIDE and 1 <= ws <= MAX_SOURCE_SIDE):
@@ -214,13 +295,18 @@ class ClipResizer:
             if off < 0 or off + int(T) * hs * ws * 3 > n:
                 raise KernelError(f"clip {b}: bytes [{off}, {off + int(T) * hs * ws * 3}) leave the packed buffer "
                                   f"of {n} bytes")
+            if win:
+                y0, x0, hc, wc = win
+                if y0 < 0 or x0 < 0 or hc < 1 or wc < 1 or y0 + hc > hs or x0 + wc > ws:
+                    raise KernelError(f"clip {b}: window rows [{y0}, {y0 + hc}) x columns [{x0}, {x0 + wc}) is "
+                                      f"empty or leaves the {hs}x{ws} frame")
 
     def __call__(self, packed, desc, T):
         self.check(packed, desc, T)
         p = packed.to(self.device, non_blocking=True)
         d = desc.to(self.device, non_blocking=True)
-        return K.frames_resize_normalize(p.contiguous(), d.contiguous(), int(T), self.out_hw, self.mean, self.std,
-                                         self.bgr_swap)
+        op = K.frames_crop_resize_normalize if desc.shape[1] == 8 else K.frames_resize_normalize
+        return op(p.contiguous(), d.contiguous(), int(T), self.out_hw, self.mean, self.std, self.bgr_swap)
 
 
 def resolve_cut_ties(noise, num_mask):

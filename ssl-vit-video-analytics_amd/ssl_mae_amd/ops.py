@@ -1426,6 +1426,23 @@ def frames_resize_normalize(packed, desc, T, out_hw, mean, std, bgr_swap=True):
                                                      bool(bgr_swap))
 
 
+@_op("frames_crop_resize_normalize", "(Tensor packed, Tensor desc, int T, int[] out_hw, float[] mean, float[] std, "
+                                     "bool bgr_swap) -> Tensor")
+def _frames_crop_resize_normalize(packed, desc, T, out_hw, mean, std, bgr_swap):
+    return _K.frames_crop_resize_normalize(packed, desc, T, out_hw, mean, std, bgr_swap)
+
+
+@_frames_crop_resize_normalize.register_fake
+def _(packed, desc, T, out_hw, mean, std, bgr_swap):
+    return packed.new_empty((desc.shape[0], 3, T, out_hw[0], out_hw[1]), dtype=torch.float32)
+
+
+def frames_crop_resize_normalize(packed, desc, T, out_hw, mean, std, bgr_swap=True):
+    return torch.ops.ssl_mae.frames_crop_resize_normalize(packed, desc, int(T), [int(x) for x in out_hw],
+                                                          [float(x) for x in mean], [float(x) for x in std],
+                                                          bool(bgr_swap))
+
+
 # ============================================================================ streaming dynamic inference
 @_op("motion_scores", "(Tensor clip) -> Tensor")
 def _motion_scores(clip):

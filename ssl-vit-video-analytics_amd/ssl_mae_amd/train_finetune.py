@@ -18,6 +18,12 @@ for every parameter group; the non-finite skip happens inside it, so optim.GradS
 shim).  `optimizer.type: adamw_torch` keeps torch.optim.AdamW over the same groups.  The running
 loss stays on the device: one read-back per log_interval and one per epoch.  Without
 `dataset.train_split` the driver runs on labelled synthetic clips (driver.SyntheticClips).
+
+`augment.enabled` (off by default; the reference has no augmentation) gives every training clip a
+random-resized crop and a horizontal flip, the same for all its frames and fresh in every epoch
+(mae_loader.RandomResizedCropFlip, seeded from runtime.seed): the window goes into the
+descriptor of the one resize launch (sm_frames_crop_resize_normalize), so it costs no pixel work
+on the host.  The validation loader is never augmented.
 """
 import argparse
 import functools
@@ -46,6 +52,7 @@ DEFAULTS = {
     "model": {"embed_dim": 576, "pretrained_ssl": None, "freeze_backbone": False},
     "optimizer": {"type": "adamw"},
     "evaluation": {"topk": [1, 5]},
+    "augment": {"enabled": False, "scale": [0.35, 1.0], "ratio": [0.75, 1.3333], "flip": 0.5},
     "synthetic": {"num_train": 96, "num_val": 32},
     "runtime": {"seed": 42, "num_workers": 4},
     "paths": {"save_dir": "results/finetune", "log_dir": "results/logs"},
@@ -55,8 +62,9 @@ DEFAULTS = {
 def resolve_config(cfg, mode=None, pretrained_ssl=None, epochs=None, batch_size=None, save_dir=None,
                    optimizer=None):
     """The file's values over DEFAULTS, the command line over both; unknown sections or keys
-    raise, and so do an unknown mode, two_stage without stage1_epochs and an SSL mode whose
-    checkpoint is missing (train_finetune.py:198-210, :284-286, :306-307)."""
+    raise, and so do an unknown mode, two_stage without stage1_epochs, an SSL mode whose
+    checkpoint is missing (train_finetune.py:198-210, :284-286, :306-307) and an `augment` section
+    out of range or enabled without a training split."""
     out = driver.merge_config(DEFAULTS, cfg)
     tr = out["training"]
     out["experiment"]["mode"] = resolve_mode(out, mode)
@@ -93,6 +101,19 @@ def resolve_config(cfg, mode=None, pretrained_ssl=None, epochs=None, batch_size=
         raise RuntimeError("[ERROR] SSL mode selected but pretrained_ssl checkpoint not found!")
     if out["dataset"]["train_split"] and not out["dataset"]["val_split"]:
         raise ValueError("[ERROR] dataset.val_split is needed with dataset.train_split")
+    aug = out["augment"]
+    for key in ("scale", "ratio"):
+        if not isinstance(aug[key], (list, tuple)) or len(aug[key]) != 2:
+            raise ValueError(f"[ERROR] augment.{key}={aug[key]}: needs a [low, high] pair")
+    if not 0.0 < float(aug["scale"][0]) <= float(aug["scale"][1]) <= 1.0:
+        raise ValueError(f"[ERROR] augment.scale={aug['scale']}: needs 0 < scale[0] <= scale[1] <= 1")
+    if not 0.0 < float(aug["ratio"][0]) <= float(aug["ratio"][1]):
+        raise ValueError(f"[ERROR] augment.ratio={aug['ratio']}: needs 0 < ratio[0] <= ratio[1]")
+    if not 0.0 <= float(aug["flip"]) <= 1.0:
+        raise ValueError(f"[ERROR] augment.flip={aug['flip']}: must lie in [0, 1]")
+    if aug["enabled"] and not out["dataset"]["train_split"]:
+        raise ValueError("[ERROR] augment.enabled needs dataset.train_split: the synthetic clips are drawn on the "
+                         "device at image_size and have no source frames to crop")
     return out
 
 
@@ -163,17 +184,22 @@ def save_checkpoint(model, epoch, acc1, save_dir, log):
 
 
 def build_loaders(cfg, device):
-    """(training loader: shuffled, drop_last; validation loader, seed + 999)."""
+    """(training loader: shuffled, drop_last, augmented when `augment.enabled`; validation loader,
+    seed + 999, never augmented)."""
     ds, tr, seed = cfg["dataset"], cfg["training"], int(cfg["runtime"]["seed"])
     bs = int(tr["batch_size"])
     if ds["train_split"]:
-        def of(split, shuffle, s):
+        def of(split, shuffle, s, **kw):
             return driver.split_file_loader(str(split), clip_len=ds["clip_len"], stride=ds["stride"],
                                             image_size=ds["image_size"], batch_size=bs,
                                             num_workers=cfg["runtime"]["num_workers"], device=device,
-                                            shuffle=shuffle, drop_last=shuffle, seed=s)
+                                            shuffle=shuffle, drop_last=shuffle, seed=s, **kw)
 
-        return of(ds["train_split"], True, seed), of(ds["val_split"], False, seed + 999)
+        aug, kw = cfg["augment"], {}
+        if aug["enabled"]:
+            from .mae_loader import RandomResizedCropFlip
+            kw["augment"] = RandomResizedCropFlip(aug["scale"], aug["ratio"], aug["flip"], seed=seed)
+        return of(ds["train_split"], True, seed, **kw), of(ds["val_split"], False, seed + 999)
     train_set = driver.SyntheticClips(cfg, int(cfg["synthetic"]["num_train"]), seed, device)
     val_set = driver.SyntheticClips(cfg, int(cfg["synthetic"]["num_val"]), seed + 999, device)
     return train_set.loader(train_set.items(), bs, True, seed), val_set.loader(val_set.items(), bs, False, seed + 999)
@@ -204,6 +230,10 @@ def main(argv=None, hooks=None):
     save_dir = Path(cfg["paths"]["save_dir"]) / mode
     save_dir.mkdir(parents=True, exist_ok=True)
     train_loader, val_loader = build_loaders(cfg, device)
+    if cfg["augment"]["enabled"]:
+        aug = cfg["augment"]
+        print(f"[INFO] Augmentation: clip-consistent random-resized crop scale={list(aug['scale'])} "
+              f"ratio={list(aug['ratio'])}, flip p={aug['flip']} (training split only, seed {cfg['runtime']['seed']})")
 
     def load_for_mode(model, ssl):
         if mode == "ft_random":
