@@ -15,7 +15,7 @@
 #include "fed_table.h"
 #include "sm_api.h"
 
-using namespace fedtab;   // the table view and the argument check, shared with fed_dp.hip
+using namespace fedtab;   // the table view, the launch helpers and the argument check, shared with fed_dp.hip and fed_q8.hip
 
 // The reference rounds x * w and acc + (x * w) separately: this file is compiled
 // with -ffp-contract=off (build.py FILE_FLAGS) so no FMA is formed.
@@ -82,6 +82,11 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 // Sources and destinations may alias (in-place aggregation): a lane loads its elements
 // from every source before its first store, lanes own disjoint elements, and no pointer
 // here is __restrict__.
+// The kernel keeps a lane layout of its own (whole 16-byte groups tid, tid + 256 of an aligned chunk, a
+// stride-256 scalar tail, stride-256 elements of a misaligned one) instead of fed_table.h's load_lane /
+// for_sources / store_dsts: load_group's 16-byte and element-wise forms write the same registers, the
+// wait that orders them sits in front of every 16-byte load, and the copy-bound launches here ran 1.28x
+// (4 sources) and 1.29x (8 sources) as long on them (profiles/fed_cleanup_isa_and_ab.txt).
 constexpr int kVecPerLane = kChunk / (256 * 4);   // float4 groups per lane per source
 static_assert(kChunk % 1024 == 0, "a chunk is a whole number of 256-lane float4 rows");
 
@@ -206,21 +211,10 @@ extern "C" int sm_fedavg_exchange(int num_src, const int32_t* src_models, const 
   const int rc = exchange_args(num_src, src_models, weights, num_dst, dst_models, table, table_bytes, 4, st, a, h);
   const int64_t chunks = h.num_chunks;
   if (rc != 0 || chunks == 0) return rc;
-  // 8 resident 256-lane blocks per CU on 256 CUs, grid-stride over chunks beyond that.
-  const dim3 g((unsigned)(chunks < 2048 ? chunks : 2048)), b(256);
+  const dim3 g = exchange_grid(chunks), b(256);
   const unsigned char* tab = (const unsigned char*)table;
-  if (copy_only) {
-    hipLaunchKernelGGL((fedavg_exchange_kernel<1, true>), g, b, 0, st, a, tab);
-  } else {
-    switch (num_src) {
-      case 1: hipLaunchKernelGGL((fedavg_exchange_kernel<1, false>), g, b, 0, st, a, tab); break;
-      case 2: hipLaunchKernelGGL((fedavg_exchange_kernel<2, false>), g, b, 0, st, a, tab); break;
-      case 3: hipLaunchKernelGGL((fedavg_exchange_kernel<3, false>), g, b, 0, st, a, tab); break;
-      case 4: hipLaunchKernelGGL((fedavg_exchange_kernel<4, false>), g, b, 0, st, a, tab); break;
-      case 8: hipLaunchKernelGGL((fedavg_exchange_kernel<8, false>), g, b, 0, st, a, tab); break;
-      default: hipLaunchKernelGGL((fedavg_exchange_kernel<0, false>), g, b, 0, st, a, tab); break;
-    }
-  }
+  if (copy_only) hipLaunchKernelGGL((fedavg_exchange_kernel<1, true>), g, b, 0, st, a, tab);
+  else FED_DISPATCH_KC(num_src, hipLaunchKernelGGL((fedavg_exchange_kernel<KC, false>), g, b, 0, st, a, tab));
   SM_CHECK_LAUNCH();
   return 0;
 }
@@ -233,8 +227,8 @@ extern "C" int sm_fedavg_exchange_counters(int num_src, const int32_t* src_model
   const int rc = exchange_args(num_src, src_models, nullptr, num_dst, dst_models, table, table_bytes, 8, st, a, h);
   const int64_t chunks = h.num_chunks;
   if (rc != 0 || chunks == 0) return rc;
-  hipLaunchKernelGGL(fedavg_exchange_counters_kernel, dim3((unsigned)(chunks < 2048 ? chunks : 2048)), dim3(256), 0,
-                     st, a, (const unsigned char*)table);
+  hipLaunchKernelGGL(fedavg_exchange_counters_kernel, exchange_grid(chunks), dim3(256), 0, st, a,
+                     (const unsigned char*)table);
   SM_CHECK_LAUNCH();
   return 0;
 }
@@ -255,18 +249,8 @@ extern "C" int sm_fedavg_weighted_sum(int num_clients, const float* const* clien
   int64_t done = 0;
   if (vec && n >= 4) {
     const int64_t n4 = n / 4;
-    // 8 resident 256-lane blocks per CU on 256 CUs, grid-stride beyond that.
-    int64_t blocks = (n4 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    const dim3 g((unsigned)blocks), b(256);
-    switch (num_clients) {
-      case 1: hipLaunchKernelGGL(fedavg_sum4_kernel<1>, g, b, 0, st, c, num_clients, n4, out); break;
-      case 2: hipLaunchKernelGGL(fedavg_sum4_kernel<2>, g, b, 0, st, c, num_clients, n4, out); break;
-      case 3: hipLaunchKernelGGL(fedavg_sum4_kernel<3>, g, b, 0, st, c, num_clients, n4, out); break;
-      case 4: hipLaunchKernelGGL(fedavg_sum4_kernel<4>, g, b, 0, st, c, num_clients, n4, out); break;
-      case 8: hipLaunchKernelGGL(fedavg_sum4_kernel<8>, g, b, 0, st, c, num_clients, n4, out); break;
-      default: hipLaunchKernelGGL(fedavg_sum4_kernel<0>, g, b, 0, st, c, num_clients, n4, out); break;
-    }
+    const dim3 g = exchange_grid((n4 + 255) / 256), b(256);   // grid-stride over the float4 groups beyond the cap
+    FED_DISPATCH_KC(num_clients, hipLaunchKernelGGL(fedavg_sum4_kernel<KC>, g, b, 0, st, c, num_clients, n4, out));
     SM_CHECK_LAUNCH();
     done = n4 * 4;
   }

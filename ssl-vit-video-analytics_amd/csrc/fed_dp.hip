@@ -55,36 +55,13 @@ __global__ void __launch_bounds__(256) dp_norms_kernel(ExchangeArgs a, int theta
       continue;
     }
     const int n = (int)n64;
-    uint64_t bits = t.addr[theta * t.S + seg];
-    for (int j = 0; j < k; ++j) bits |= t.addr[a.src[j] * t.S + seg];
-    const bool vec = (bits & 15u) == 0;
-    const float* th = seg_ptr(t, theta, seg, off);
+    const bool vec = seg_aligned(t, a, k, seg, false, t.addr[theta * t.S + seg]);
     f32x4 g[kGroups];
-#pragma unroll
-    for (int u = 0; u < kGroups; ++u) g[u] = load_group(th, 4 * (tid + 256 * u), n, vec);
-    if constexpr (KC > 0) {
-      f32x4 x[KC][kGroups];
-#pragma unroll
-      for (int j = 0; j < KC; ++j) {
-        const float* p = seg_ptr(t, a.src[j], seg, off);
-#pragma unroll
-        for (int u = 0; u < kGroups; ++u) x[j][u] = load_group(p, 4 * (tid + 256 * u), n, vec);
-      }
-#pragma unroll
-      for (int j = 0; j < KC; ++j) {
-        const double s = wave_sum_d((double)lane_sq(x[j], g));
-        if (lane == 0) red[wv][j] = s;
-      }
-    } else {
-      for (int j = 0; j < k; ++j) {
-        const float* p = seg_ptr(t, a.src[j], seg, off);
-        f32x4 x[kGroups];
-#pragma unroll
-        for (int u = 0; u < kGroups; ++u) x[u] = load_group(p, 4 * (tid + 256 * u), n, vec);
-        const double s = wave_sum_d((double)lane_sq(x, g));
-        if (lane == 0) red[wv][j] = s;
-      }
-    }
+    load_lane(seg_ptr(t, theta, seg, off), n, vec, g);
+    for_sources<KC>(t, a, k, seg, off, n, vec, [&](int j, const f32x4* x) {
+      const double s = wave_sum_d((double)lane_sq(x, g));
+      if (lane == 0) red[wv][j] = s;
+    });
     __syncthreads();
     if (tid < k) part[tid * t.C + c] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
     __syncthreads();   // red is written again in the block's next chunk
@@ -134,26 +111,22 @@ __global__ void __launch_bounds__(256) dp_update_kernel(ExchangeArgs a, int thet
     if (!chunk_range(t, c, seg, off, n64)) continue;
     const int n = (int)n64;
     const bool clip = seg_clip[seg] != 0;   // block-uniform
-    uint64_t bits = t.addr[theta * t.S + seg];
-    for (int j = 0; j < k; ++j) bits |= t.addr[a.src[j] * t.S + seg];
-    for (int d = 0; d < a.num_dst; ++d) bits |= t.addr[a.dst[d] * t.S + seg];
-    const bool vec = (bits & 15u) == 0;
+    const bool vec = seg_aligned(t, a, k, seg, true, t.addr[theta * t.S + seg]);
     f32x4 acc[kGroups], g[kGroups];
 #pragma unroll
     for (int u = 0; u < kGroups; ++u) acc[u] = g[u] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (clip) {
-      const float* th = seg_ptr(t, theta, seg, off);
+      load_lane(seg_ptr(t, theta, seg, off), n, vec, g);
 #pragma unroll
-      for (int u = 0; u < kGroups; ++u) acc[u] = g[u] = load_group(th, 4 * (tid + 256 * u), n, vec);
+      for (int u = 0; u < kGroups; ++u) acc[u] = g[u];
     }
+    // for_sources with the clip test in its operation, or around two of them, costs dp_update_kernel<4>
+    // a wave (73 and 81 VGPRs against 70: the kernel sits at the SGPR ceiling and spills into VGPR
+    // lanes), so the two-shaped loop stays written out here.
     if constexpr (KC > 0) {
       f32x4 x[KC][kGroups];
 #pragma unroll
-      for (int j = 0; j < KC; ++j) {
-        const float* p = seg_ptr(t, a.src[j], seg, off);
-#pragma unroll
-        for (int u = 0; u < kGroups; ++u) x[j][u] = load_group(p, 4 * (tid + 256 * u), n, vec);
-      }
+      for (int j = 0; j < KC; ++j) load_lane(seg_ptr(t, a.src[j], seg, off), n, vec, x[j]);
 #pragma unroll
       for (int j = 0; j < KC; ++j) {
         if (clip) add_clipped(acc, x[j], g, wsc[j]);
@@ -161,10 +134,8 @@ __global__ void __launch_bounds__(256) dp_update_kernel(ExchangeArgs a, int thet
       }
     } else {
       for (int j = 0; j < k; ++j) {
-        const float* p = seg_ptr(t, a.src[j], seg, off);
         f32x4 x[kGroups];
-#pragma unroll
-        for (int u = 0; u < kGroups; ++u) x[u] = load_group(p, 4 * (tid + 256 * u), n, vec);
+        load_lane(seg_ptr(t, a.src[j], seg, off), n, vec, x);
         if (clip) add_clipped(acc, x, g, wsc[j]);
         else add_plain(acc, x, a.w[j]);
       }
@@ -179,11 +150,7 @@ __global__ void __launch_bounds__(256) dp_update_kernel(ExchangeArgs a, int thet
           acc[u][e] = fmaf(noise_std, gauss_draw(rk, col * kColMul), acc[u][e]);
         }
     }
-    for (int d = 0; d < a.num_dst; ++d) {
-      float* q = (float*)t.addr[a.dst[d] * t.S + seg] + off;
-#pragma unroll
-      for (int u = 0; u < kGroups; ++u) store_group(q, 4 * (tid + 256 * u), n, vec, acc[u]);
-    }
+    store_dsts(t, a, seg, off, n, vec, acc);
   }
 }
 
@@ -235,32 +202,17 @@ extern "C" int sm_fedavg_dp_exchange(int num_src, const int32_t* src_models, con
   if (!ws || ((uintptr_t)ws & 15u) || ws_bytes < sm_fedavg_dp_exchange_workspace_bytes(num_src, chunks)) return -4;
   double* part = (double*)ws;
   float* wsc = (float*)(part + num_src * chunks);
-  // 8 resident 256-lane blocks per CU on 256 CUs, grid-stride over chunks beyond that.
-  const dim3 g((unsigned)(chunks < 2048 ? chunks : 2048)), b(256);
+  const dim3 g = exchange_grid(chunks), b(256);
   const unsigned char* tab = (const unsigned char*)table;
   const uint32_t s32 = (uint32_t)seed ^ (uint32_t)(seed >> 32);   // seed32
   if (chunks > 0) {
-    switch (num_src) {
-      case 1: hipLaunchKernelGGL(dp_norms_kernel<1>, g, b, 0, st, a, global_model, tab, seg_clip, part); break;
-      case 2: hipLaunchKernelGGL(dp_norms_kernel<2>, g, b, 0, st, a, global_model, tab, seg_clip, part); break;
-      case 3: hipLaunchKernelGGL(dp_norms_kernel<3>, g, b, 0, st, a, global_model, tab, seg_clip, part); break;
-      case 4: hipLaunchKernelGGL(dp_norms_kernel<4>, g, b, 0, st, a, global_model, tab, seg_clip, part); break;
-      case 8: hipLaunchKernelGGL(dp_norms_kernel<8>, g, b, 0, st, a, global_model, tab, seg_clip, part); break;
-      default: hipLaunchKernelGGL(dp_norms_kernel<0>, g, b, 0, st, a, global_model, tab, seg_clip, part); break;
-    }
+    FED_DISPATCH_KC(num_src, hipLaunchKernelGGL(dp_norms_kernel<KC>, g, b, 0, st, a, global_model, tab, seg_clip, part));
     SM_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL(dp_finalise_kernel, dim3((unsigned)num_src), b, 0, st, a, chunks, part, clip_norm, stats, wsc);
   SM_CHECK_LAUNCH();
   if (chunks == 0) return 0;
-  switch (num_src) {
-    case 1: hipLaunchKernelGGL(dp_update_kernel<1>, g, b, 0, st, a, global_model, tab, seg_clip, wsc, noise_std, s32); break;
-    case 2: hipLaunchKernelGGL(dp_update_kernel<2>, g, b, 0, st, a, global_model, tab, seg_clip, wsc, noise_std, s32); break;
-    case 3: hipLaunchKernelGGL(dp_update_kernel<3>, g, b, 0, st, a, global_model, tab, seg_clip, wsc, noise_std, s32); break;
-    case 4: hipLaunchKernelGGL(dp_update_kernel<4>, g, b, 0, st, a, global_model, tab, seg_clip, wsc, noise_std, s32); break;
-    case 8: hipLaunchKernelGGL(dp_update_kernel<8>, g, b, 0, st, a, global_model, tab, seg_clip, wsc, noise_std, s32); break;
-    default: hipLaunchKernelGGL(dp_update_kernel<0>, g, b, 0, st, a, global_model, tab, seg_clip, wsc, noise_std, s32); break;
-  }
+  FED_DISPATCH_KC(num_src, hipLaunchKernelGGL(dp_update_kernel<KC>, g, b, 0, st, a, global_model, tab, seg_clip, wsc, noise_std, s32));
   SM_CHECK_LAUNCH();
   return 0;
 }

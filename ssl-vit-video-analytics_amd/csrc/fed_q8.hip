@@ -146,26 +146,17 @@ __global__ void __launch_bounds__(256) q8_exchange_kernel(ExchangeArgs a, Q8Args
       if (!in_range) continue;
     }
     const int n = (int)n64;
-    uint64_t bits = t.addr[q.theta * t.S + seg];
-    for (int j = 0; j < k; ++j) bits |= t.addr[a.src[j] * t.S + seg];
-    for (int d = 0; d < a.num_dst; ++d) bits |= t.addr[a.dst[d] * t.S + seg];
-    const bool vec = (bits & 15u) == 0;
+    const bool vec = seg_aligned(t, a, k, seg, true, t.addr[q.theta * t.S + seg]);
     f32x4 acc[kGroups];
     if (seg_mode[seg] == 0) {
 #pragma unroll
       for (int u = 0; u < kGroups; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-      for (int j = 0; j < k; ++j) {
-        const float* p = seg_ptr(t, a.src[j], seg, off);
-        f32x4 x[kGroups];
-#pragma unroll
-        for (int u = 0; u < kGroups; ++u) x[u] = load_group(p, 4 * (tid + 256 * u), n, vec);
-        add_plain(acc, x, a.w[j]);
-      }
+      for_sources<0>(t, a, k, seg, off, n, vec, [&](int j, const f32x4* x) { add_plain(acc, x, a.w[j]); });
     } else {
-      const float* th = seg_ptr(t, q.theta, seg, off);
       f32x4 g[kGroups];
+      load_lane(seg_ptr(t, q.theta, seg, off), n, vec, g);
 #pragma unroll
-      for (int u = 0; u < kGroups; ++u) acc[u] = g[u] = load_group(th, 4 * (tid + 256 * u), n, vec);
+      for (int u = 0; u < kGroups; ++u) acc[u] = g[u];
       if constexpr (KC > 0) {
         constexpr int kHalf = KC > 4 ? KC / 2 : KC;   // 8 sources at once would not fit the register file
         static_assert(KC % kHalf == 0, "the sources are loaded in equal parts");
@@ -174,13 +165,8 @@ __global__ void __launch_bounds__(256) q8_exchange_kernel(ExchangeArgs a, Q8Args
           f32x4 x[kHalf][kGroups], e[kHalf][kGroups];
 #pragma unroll
           for (int j = 0; j < kHalf; ++j) {
-            const float* p = seg_ptr(t, a.src[j0 + j], seg, off);
-            const float* r = q.resid + (int64_t)(a.src[j0 + j] - 1) * (t.C * kChunk) + c * kChunk;
-#pragma unroll
-            for (int u = 0; u < kGroups; ++u) {
-              x[j][u] = load_group(p, 4 * (tid + 256 * u), n, vec);
-              e[j][u] = load_group(r, 4 * (tid + 256 * u), n, true);
-            }
+            load_lane(seg_ptr(t, a.src[j0 + j], seg, off), n, vec, x[j]);
+            load_lane(q.resid + (int64_t)(a.src[j0 + j] - 1) * (t.C * kChunk) + c * kChunk, n, true, e[j]);
           }
 #pragma unroll
           for (int j = 0; j < kHalf; ++j) q8_source(q, a, j0 + j, t.C, c, n, x[j], e[j], g, acc, red_s, red_m);
@@ -188,14 +174,9 @@ __global__ void __launch_bounds__(256) q8_exchange_kernel(ExchangeArgs a, Q8Args
       } else {
 #pragma unroll 1
         for (int j = 0; j < k; ++j) {
-          const float* p = seg_ptr(t, a.src[j], seg, off);
-          const float* r = q.resid + (int64_t)(a.src[j] - 1) * (t.C * kChunk) + c * kChunk;
           f32x4 x[kGroups], e[kGroups];
-#pragma unroll
-          for (int u = 0; u < kGroups; ++u) {
-            x[u] = load_group(p, 4 * (tid + 256 * u), n, vec);
-            e[u] = load_group(r, 4 * (tid + 256 * u), n, true);
-          }
+          load_lane(seg_ptr(t, a.src[j], seg, off), n, vec, x);
+          load_lane(q.resid + (int64_t)(a.src[j] - 1) * (t.C * kChunk) + c * kChunk, n, true, e);
           q8_source(q, a, j, t.C, c, n, x, e, g, acc, red_s, red_m);
         }
       }
@@ -209,11 +190,7 @@ __global__ void __launch_bounds__(256) q8_exchange_kernel(ExchangeArgs a, Q8Args
       }
       __syncthreads();   // red_s / red_m are written again in the block's next chunk
     }
-    for (int d = 0; d < a.num_dst; ++d) {
-      float* o = (float*)t.addr[a.dst[d] * t.S + seg] + off;
-#pragma unroll
-      for (int u = 0; u < kGroups; ++u) store_group(o, 4 * (tid + 256 * u), n, vec, acc[u]);
-    }
+    store_dsts(t, a, seg, off, n, vec, acc);
   }
 }
 
@@ -236,17 +213,9 @@ extern "C" int sm_fedavg_q8_exchange(int num_src, const int32_t* src_models, con
   const int64_t chunks = h.num_chunks;
   if (chunks == 0) return 0;
   const Q8Args q{resid, codes, scales, part, global_model, h.num_models, h.num_segments, h.num_chunks};
-  // 8 resident 256-lane blocks per CU on 256 CUs, grid-stride over chunks beyond that.
-  const dim3 g((unsigned)(chunks < 2048 ? chunks : 2048)), b(256);
+  const dim3 g = exchange_grid(chunks), b(256);
   const unsigned char* tab = (const unsigned char*)table;
-  switch (num_src) {
-    case 1: hipLaunchKernelGGL(q8_exchange_kernel<1>, g, b, 0, st, a, q, tab, seg_mode); break;
-    case 2: hipLaunchKernelGGL(q8_exchange_kernel<2>, g, b, 0, st, a, q, tab, seg_mode); break;
-    case 3: hipLaunchKernelGGL(q8_exchange_kernel<3>, g, b, 0, st, a, q, tab, seg_mode); break;
-    case 4: hipLaunchKernelGGL(q8_exchange_kernel<4>, g, b, 0, st, a, q, tab, seg_mode); break;
-    case 8: hipLaunchKernelGGL(q8_exchange_kernel<8>, g, b, 0, st, a, q, tab, seg_mode); break;
-    default: hipLaunchKernelGGL(q8_exchange_kernel<0>, g, b, 0, st, a, q, tab, seg_mode); break;
-  }
+  FED_DISPATCH_KC(num_src, hipLaunchKernelGGL(q8_exchange_kernel<KC>, g, b, 0, st, a, q, tab, seg_mode));
   SM_CHECK_LAUNCH();
   return 0;
 }

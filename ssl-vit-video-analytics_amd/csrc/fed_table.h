@@ -1,5 +1,7 @@
 // The FedAvg exchange table (include/sm_api.h "FedAvg exchange table") as the kernels of
-// csrc/fed.hip, csrc/fed_dp.hip and csrc/fed_q8.hip see it, and the host-side check of a launch's arguments.
+// csrc/fed.hip, csrc/fed_dp.hip and csrc/fed_q8.hip see it, the pieces of a chunk's exchange that they
+// share (a lane's loads and stores, the alignment test, the source loop; the launch grid and the
+// dispatch over the source count), and the host-side check of a launch's arguments.
 #pragma once
 #include "common.h"
 #include "sm_api.h"
@@ -54,7 +56,8 @@ SM_DEV bool chunk_range(const TableView& t, int64_t c, int64_t& seg, int64_t& of
 }
 
 // ---- a lane's share of a chunk in csrc/fed_dp.hip and csrc/fed_q8.hip: the 4-element groups tid and
-// tid + 256 of the chunk, in the 16-byte form and in the element-wise form alike.
+// tid + 256 of the chunk, in the 16-byte form and in the element-wise form alike.  (fedavg_exchange_kernel
+// in csrc/fed.hip keeps a layout of its own: see there.)
 constexpr int kGroups = kChunk / (256 * 4);   // 4-element groups per lane per model
 static_assert(kChunk % 1024 == 0, "a chunk is a whole number of 256-lane float4 rows");
 
@@ -90,6 +93,79 @@ SM_DEV void add_plain(f32x4* acc, const f32x4* x, float w) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc[u][e] = __fadd_rn(acc[u][e], __fmul_rn(x[u][e], w));
 }
+
+// A lane's kGroups groups of a chunk of n elements at p.
+SM_DEV void load_lane(const float* p, int n, bool vec, f32x4* x) {
+#pragma unroll
+  for (int u = 0; u < kGroups; ++u) x[u] = load_group(p, 4 * ((int)threadIdx.x + 256 * u), n, vec);
+}
+
+SM_DEV void store_lane(float* q, int n, bool vec, const f32x4* v) {
+#pragma unroll
+  for (int u = 0; u < kGroups; ++u) store_group(q, 4 * ((int)threadIdx.x + 256 * u), n, vec, v[u]);
+}
+
+// Segment `seg` 16-byte aligned in the k sources, with_dst in the destinations too, and at `more`
+// (the address of a model that is neither, such as theta's; 0: none).
+SM_DEV bool seg_aligned(const TableView& t, const ExchangeArgs& a, int k, int64_t seg, bool with_dst,
+                        uint64_t more = 0) {
+  uint64_t bits = more;
+  for (int j = 0; j < k; ++j) bits |= t.addr[a.src[j] * t.S + seg];
+  if (with_dst)
+    for (int d = 0; d < a.num_dst; ++d) bits |= t.addr[a.dst[d] * t.S + seg];
+  return (bits & 15u) == 0;
+}
+
+// f(j, x) for every source j in source order, x the lane's groups of source j.  KC > 0: source count
+// known at compile time, every load of the lane is issued before the first f; KC == 0: runtime count k.
+// Followed by store_dsts this keeps in-place exchange sound: a lane has loaded its elements from
+// every source before its first store, and lanes own disjoint elements.
+template <int KC, class F>
+SM_DEV void for_sources(const TableView& t, const ExchangeArgs& a, int k, int64_t seg, int64_t off, int n, bool vec,
+                        F&& f) {
+  if constexpr (KC > 0) {
+    // every source's address first: an address read between two sources' loads would wait for the
+    // loads before it
+    const float* p[KC];
+    f32x4 x[KC][kGroups];
+#pragma unroll
+    for (int j = 0; j < KC; ++j) p[j] = seg_ptr(t, a.src[j], seg, off);
+#pragma unroll
+    for (int j = 0; j < KC; ++j) load_lane(p[j], n, vec, x[j]);
+#pragma unroll
+    for (int j = 0; j < KC; ++j) f(j, x[j]);
+  } else {
+    for (int j = 0; j < k; ++j) {
+      f32x4 x[kGroups];
+      load_lane(seg_ptr(t, a.src[j], seg, off), n, vec, x);
+      f(j, x);
+    }
+  }
+}
+
+// acc into every destination of the launch.
+SM_DEV void store_dsts(const TableView& t, const ExchangeArgs& a, int64_t seg, int64_t off, int n, bool vec,
+                       const f32x4* acc) {
+  for (int d = 0; d < a.num_dst; ++d) store_lane((float*)t.addr[a.dst[d] * t.S + seg] + off, n, vec, acc);
+}
+
+// One block per chunk (per 256 float4 groups in the weighted sum) up to 8 resident 256-lane blocks
+// per CU on 256 CUs, grid-stride beyond that.
+inline dim3 exchange_grid(int64_t blocks) { return dim3((unsigned)(blocks < 2048 ? blocks : 2048)); }
+
+// Run the statement(s) with constexpr int KC = NUM_SRC where the kernels are instantiated for that
+// count, else 0 (their runtime-count form).
+#define FED_DISPATCH_KC(NUM_SRC, ...)                              \
+  do {                                                             \
+    switch (NUM_SRC) {                                             \
+      case 1: { constexpr int KC = 1; __VA_ARGS__; } break;        \
+      case 2: { constexpr int KC = 2; __VA_ARGS__; } break;        \
+      case 3: { constexpr int KC = 3; __VA_ARGS__; } break;        \
+      case 4: { constexpr int KC = 4; __VA_ARGS__; } break;        \
+      case 8: { constexpr int KC = 8; __VA_ARGS__; } break;        \
+      default: { constexpr int KC = 0; __VA_ARGS__; } break;       \
+    }                                                              \
+  } while (0)
 
 // Counts, model indices and the table's header (read back from the device: 64 bytes, once
 // per launch) against table_bytes and the entry point's element size.  0, or -2.

@@ -1101,17 +1101,24 @@ def fedavg_exchange_table(models, dtype):
     return table, addr.tolist()
 
 
-def _fedavg_exchange_call(name, src_models, weights, dst_models, table, extra):
+def _fedavg_exchange_call(name, src_models, weights, dst_models, table, extra, global_model=None):
+    """What the exchange entry points share: the table check, the source / weight count check and
+    the leading arguments (sources, weights if any, the global model if any, destinations, table);
+    `extra` is the entry point's own trailing arguments."""
     import ctypes
     _chk(table)
     if table.dtype != torch.uint8 or not table.is_contiguous():
         raise _lib.KernelError(f"{name}: the table is a contiguous uint8 device tensor (fedavg_exchange_table)")
+    if weights is not None and len(weights) != len(src_models):
+        raise _lib.KernelError(f"{name}: {len(src_models)} sources but {len(weights)} weights")
     src = (ctypes.c_int32 * max(1, len(src_models)))(*[int(i) for i in src_models])
     dst = (ctypes.c_int32 * max(1, len(dst_models)))(*[int(i) for i in dst_models])
     args = [len(src_models), ctypes.cast(src, ctypes.c_void_p)]
     if weights is not None:
         ws = (ctypes.c_float * max(1, len(weights)))(*[float(w) for w in weights])
         args.append(ctypes.cast(ws, ctypes.c_void_p))
+    if global_model is not None:
+        args.append(int(global_model))
     args += [len(dst_models), ctypes.cast(dst, ctypes.c_void_p), ptr(table), table.numel()] + extra + [stream()]
     call("sm_" + name, *args)
 
@@ -1120,8 +1127,6 @@ def fedavg_exchange(src_models, weights, dst_models, table, copy_only=False):
     """One launch over an fp32 cohort table: the weighted sum of the source models' segments in
     source order (fedavg_weighted_sum's arithmetic, bit for bit) -- or, with copy_only, the one
     source's bits -- written into every destination model's segments, which may be sources too."""
-    if not copy_only and len(weights) != len(src_models):
-        raise _lib.KernelError(f"fedavg_exchange: {len(src_models)} sources but {len(weights)} weights")
     if copy_only:
         weights = [1.0] * len(src_models)
     _fedavg_exchange_call("fedavg_exchange", src_models, weights, dst_models, table, [1 if copy_only else 0])
@@ -1141,13 +1146,7 @@ def fedavg_dp_exchange(src_models, weights, global_model, dst_models, table, num
     into every destination model.  `num_chunks` is the table's chunk count (it sizes the
     workspace); seg_clip is a uint8 device tensor with one byte per segment of the table.
     -> stats, fp32 [2 * sources] on the device: the update norms, then the clip scales."""
-    import ctypes
     _chk(table, seg_clip, stats, ws)
-    if table.dtype != torch.uint8 or not table.is_contiguous():
-        raise _lib.KernelError("fedavg_dp_exchange: the table is a contiguous uint8 device tensor "
-                               "(fedavg_exchange_table)")
-    if len(weights) != len(src_models):
-        raise _lib.KernelError(f"fedavg_dp_exchange: {len(src_models)} sources but {len(weights)} weights")
     if seg_clip is not None and (seg_clip.dtype != torch.uint8 or not seg_clip.is_contiguous()):
         raise _lib.KernelError("fedavg_dp_exchange: seg_clip is a contiguous uint8 device tensor")
     k = len(src_models)
@@ -1157,13 +1156,9 @@ def fedavg_dp_exchange(src_models, weights, global_model, dst_models, table, num
         raise _lib.KernelError("fedavg_dp_exchange: stats must be contiguous fp32 [2 * sources]")
     if ws is None:
         ws = _ws(max(query("sm_fedavg_dp_exchange_workspace_bytes", k, int(num_chunks)), 0), table.device)
-    src = (ctypes.c_int32 * max(1, k))(*[int(i) for i in src_models])
-    dst = (ctypes.c_int32 * max(1, len(dst_models)))(*[int(i) for i in dst_models])
-    wts = (ctypes.c_float * max(1, k))(*[float(w) for w in weights])
-    call("sm_fedavg_dp_exchange", k, ctypes.cast(src, ctypes.c_void_p), ctypes.cast(wts, ctypes.c_void_p),
-         int(global_model), len(dst_models), ctypes.cast(dst, ctypes.c_void_p), ptr(table), table.numel(),
-         ptr(seg_clip), float(clip_norm), float(noise_std), int(seed) & ((1 << 64) - 1), ptr(stats), ptr(ws),
-         ws.numel(), stream())
+    _fedavg_exchange_call("fedavg_dp_exchange", src_models, weights, dst_models, table,
+                          [ptr(seg_clip), float(clip_norm), float(noise_std), int(seed) & ((1 << 64) - 1), ptr(stats),
+                           ptr(ws), ws.numel()], global_model=global_model)
     return stats
 
 
@@ -1182,13 +1177,8 @@ def fedavg_q8_exchange(src_models, weights, global_model, dst_models, table, num
     the clients upload when both are given.
     -> part, fp64 [sources, num_chunks, 2] on the device: per chunk, max |v| and the sum of squares
     of the new residual."""
-    import ctypes
     _chk(table, seg_mode, resid, codes, scales, part)
     name = "fedavg_q8_exchange"
-    if table.dtype != torch.uint8 or not table.is_contiguous():
-        raise _lib.KernelError(f"{name}: the table is a contiguous uint8 device tensor (fedavg_exchange_table)")
-    if len(weights) != len(src_models):
-        raise _lib.KernelError(f"{name}: {len(src_models)} sources but {len(weights)} weights")
     if seg_mode is not None and (seg_mode.dtype != torch.uint8 or not seg_mode.is_contiguous()):
         raise _lib.KernelError(f"{name}: seg_mode is a contiguous uint8 device tensor")
     k, C = len(src_models), int(num_chunks)
@@ -1210,12 +1200,9 @@ def fedavg_q8_exchange(src_models, weights, global_model, dst_models, table, num
         part = torch.empty((max(k, 1), C, 2), dtype=torch.float64, device=table.device)
     elif part.dtype != torch.float64 or part.numel() != 2 * k * C or not part.is_contiguous():
         raise _lib.KernelError(f"{name}: part must be contiguous fp64 [{k}, {C}, 2]")
-    src = (ctypes.c_int32 * max(1, k))(*[int(i) for i in src_models])
-    dst = (ctypes.c_int32 * max(1, len(dst_models)))(*[int(i) for i in dst_models])
-    wts = (ctypes.c_float * max(1, k))(*[float(w) for w in weights])
-    call("sm_fedavg_q8_exchange", k, ctypes.cast(src, ctypes.c_void_p), ctypes.cast(wts, ctypes.c_void_p),
-         int(global_model), len(dst_models), ctypes.cast(dst, ctypes.c_void_p), ptr(table), table.numel(),
-         ptr(seg_mode), ptr(resid), int(rows), ptr(codes), ptr(scales), ptr(part), stream())
+    _fedavg_exchange_call(name, src_models, weights, dst_models, table,
+                          [ptr(seg_mode), ptr(resid), int(rows), ptr(codes), ptr(scales), ptr(part)],
+                          global_model=global_model)
     return part
 
 

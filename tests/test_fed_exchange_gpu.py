@@ -11,7 +11,8 @@ import torch.nn as nn
 
 pytestmark = pytest.mark.gpu
 
-SEG_LENS = (1, 3, 4, 5, 96, 257, 4099, 1_000_003)
+# 2047, 2048, 2049: the edge of a 2048-element chunk, with and without a whole last 4-element group
+SEG_LENS = (1, 3, 4, 5, 96, 257, 4099, 1_000_003, 2047, 2048, 2049)
 # segment index -> the models whose copy of it starts 4 bytes off a 16-byte boundary
 # (model 0 is the destination, models 1..K the sources; -1 = the last source)
 MISALIGNED = {4: (-1,), 6: (0,)}
@@ -113,6 +114,42 @@ def test_copy_only_is_a_bit_copy():
     for p in range(4):
         for s in range(len(SEG_LENS)):
             assert np.array_equal(models[p][s].cpu().numpy().view(np.int32), src[s]), (p, SEG_LENS[s])
+
+
+@pytest.mark.parametrize("k", [3, 5])           # a compile-time and a runtime source count
+def test_exchange_into_a_misaligned_destination_only(k):
+    """A multi-chunk segment that is 16-byte aligned in every source and in one destination, and 4
+    bytes off in another destination that is no source: both receive the oracle's bits."""
+    from oracle import fedavg_oracle as O
+    from ssl_mae_amd import federated as F
+    from ssl_mae_amd import kernels as K
+    n = 4099                                     # two whole chunks and a 3-element tail
+    rng = np.random.default_rng(40 + k)
+    host = [rng.standard_normal(n).astype(np.float32) for _ in range(k)]
+    w = [float(x) for x in rng.integers(1, 1000, k)]
+    fill = np.full(n, 7.0, dtype=np.float32)
+    models = [[_segment(fill, True)]] + [[_segment(h, False)] for h in host] + [[_segment(fill, False)]]
+    table, _ = K.fedavg_exchange_table(models, torch.float32)
+    K.fedavg_exchange(list(range(1, k + 1)), F._norm_weights(w, float(sum(w))), [0, k + 1], table)
+    want = O.weighted_sum(host, w)
+    _assert_bits(models[0][0].cpu().numpy(), want, (k, "misaligned destination"))
+    _assert_bits(models[k + 1][0].cpu().numpy(), want, (k, "aligned destination"))
+    for j in range(k):                           # sources untouched
+        assert np.array_equal(models[j + 1][0].cpu().numpy().view(np.int32), host[j].view(np.int32))
+
+
+def test_copy_only_into_a_misaligned_destination():
+    from ssl_mae_amd import kernels as K
+    n = 2049                                     # a whole chunk and a chunk of one element
+    rng = np.random.default_rng(5)
+    src = rng.integers(-2 ** 31, 2 ** 31 - 1, n, dtype=np.int64).astype(np.int32)
+    src[-4:] = np.array([0x80000000, 0x7fc12345, 0x7f812345, 0xff800000], dtype=np.uint32).view(np.int32)
+    zeros = np.zeros(n, dtype=np.float32)
+    models = [[_segment(src.view(np.float32), False)], [_segment(zeros, True)], [_segment(zeros, False)]]
+    table, _ = K.fedavg_exchange_table(models, torch.float32)
+    K.fedavg_exchange([0], [1.0], [1, 2], table, copy_only=True)
+    for p in range(3):
+        assert np.array_equal(models[p][0].cpu().numpy().view(np.int32), src), p
 
 
 def test_exchange_counters_max():
