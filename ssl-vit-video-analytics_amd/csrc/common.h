@@ -232,6 +232,74 @@ SM_DEV float block_sum(float v, float* red) {
   return t;
 }
 
+// Fixed-order fp64 sums of a 256-thread block (four waves).  They hold additions only, so a result
+// does not depend on the contraction mode of the file that includes them; products stay in the
+// kernels' own loops.
+//
+// waves_sum4_d: v[k] is uniform over each wave.  Lane 0 of each wave writes it to LDS, one barrier,
+// and thread 0 gets ((w0 + w1) + w2) + w3 in v[k], w the waves' values; every other thread keeps
+// its own.  block_sum4_d: v[k] is per thread: the wave butterfly (wave_sum_d) first, then the same.
+template <int K>
+SM_DEV void waves_sum4_d(double (&v)[K]) {
+  __shared__ double red[K][4];
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int k = 0; k < K; ++k) red[k][threadIdx.x >> 6] = v[k];
+  __syncthreads();
+  if (threadIdx.x == 0)
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = ((red[k][0] + red[k][1]) + red[k][2]) + red[k][3];
+}
+template <int K>
+SM_DEV void block_sum4_d(double (&v)[K]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = wave_sum_d(v[k]);
+  waves_sum4_d<K>(v);
+}
+
+// thread_order_sum_d: every thread deposits v[0..K) in LDS, one barrier, then value k of the 256
+// threads is added in thread order, (((0 + t0) + t1) + ...) + t255.  Who gets the sums: thread 0 or
+// every thread all K of them in v, or thread k < K the sum of value k in v[0].
+enum SumHolder { SUM_THREAD0, SUM_FIRST_K, SUM_EVERY_THREAD };
+template <int K, SumHolder H>
+SM_DEV void thread_order_sum_d(double (&v)[K]) {
+  __shared__ double red[256][K];
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < K; ++k) red[tid][k] = v[k];
+  __syncthreads();
+  if constexpr (H == SUM_FIRST_K) {
+    if (tid < K) {
+      double t = 0.0;
+      for (int i = 0; i < 256; ++i) t += red[i][tid];
+      v[0] = t;
+    }
+  } else if (H == SUM_EVERY_THREAD || tid == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = 0.0;
+    for (int i = 0; i < 256; ++i)
+#pragma unroll
+      for (int k = 0; k < K; ++k) v[k] += red[i][k];
+  }
+}
+
+// One wave over nb pairs part[2 i], part[2 i + 1]: lane l adds i = l, l + 64, ... ascending, then
+// the wave butterfly; s and q in every lane.
+SM_DEV void sum_pairs_d(const double* part, int nb, double& s, double& q) {
+  s = q = 0.0;
+  for (int i = threadIdx.x; i < nb; i += 64) { s += part[2 * i]; q += part[2 * i + 1]; }
+  s = wave_sum_d(s);
+  q = wave_sum_d(q);
+}
+
+// Clipping coefficient min(1, max_norm / (norm + 1e-6)) in fp32, as torch.nn.utils.clip_grad_norm_
+// forms it; a NaN quotient stays NaN (torch's clamp keeps it).  One rounded add and one rounded
+// division, no product: nothing for a contraction mode to fuse.
+SM_DEV float clip_coef(float max_norm, float norm) {
+  const float q = __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f));
+  return q < 1.f ? q : (q != q ? q : 1.f);
+}
+
 // ---------------------------------------------------------------- counter RNG
 // Dropout / DropPath masks are a pure function of (seed, row, column):
 //   h    = fmix32(seed32 + row * 0x9E3779B1 + (col >> 2) * 0x7FEB352D)
@@ -358,6 +426,21 @@ static __global__ void bn_bwd_finalize_kernel(const double* sums, int64_t M, int
 #define SM_CHECK_LAUNCH() \
   do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return (int)e__; } while (0)
 
+__host__ __device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// Grid of an elementwise grid-stride kernel: n items on 256-thread blocks, at most 8192 blocks
+inline int ew_grid(int64_t n) {
+  int64_t b = (n + 255) / 256;
+  if (b > 8192) b = 8192;
+  return b < 1 ? 1 : (int)b;
+}
+
+// Run the statement(s) with constexpr bool NAME = true when COND holds and false otherwise
+#define DISPATCH_BOOL(COND, NAME, ...)                         \
+  do {                                                         \
+    if (COND) { constexpr bool NAME = true; __VA_ARGS__; }     \
+    else { constexpr bool NAME = false; __VA_ARGS__; }         \
+  } while (0)
 // Run the statement(s) with T (T1, T2) = float for SM_F32 and __bf16 otherwise
 #define DISPATCH1(DT, ...)                                       \
   do {                                                         \

@@ -282,7 +282,7 @@ bool clip_ok(int B, int C, int T, int H, int W) {
 
 // 16-byte loads: unit pixel stride, W % 4 == 0 and every plane / row start 16-byte aligned
 bool clip_vec(const float* clip, int W, int64_t sB, int64_t sC, int64_t sT, int64_t sH, int64_t sW) {
-  return sW == 1 && W % 4 == 0 && ((uintptr_t)clip & 15) == 0 && ((sB | sC | sT | sH) & 3) == 0;
+  return sW == 1 && W % 4 == 0 && aligned16(clip) && ((sB | sC | sT | sH) & 3) == 0;
 }
 
 }  // namespace
@@ -303,10 +303,9 @@ extern "C" int sm_motion_scores(const float* clip, int B, int C, int T, int H, i
   const ClipView v{clip, sB, sC, sT, sH, sW, B, C, T, H, W};
   float* part = (float*)ws;
   if (T > 1) {
-    if (clip_vec(clip, W, sB, sC, sT, sH, sW))
-      hipLaunchKernelGGL(motion_partials_kernel<true>, dim3((unsigned)nblk), dim3(kThreads), 0, st, v, nbands, part);
-    else
-      hipLaunchKernelGGL(motion_partials_kernel<false>, dim3((unsigned)nblk), dim3(kThreads), 0, st, v, nbands, part);
+    DISPATCH_BOOL(clip_vec(clip, W, sB, sC, sT, sH, sW), VEC,
+                  hipLaunchKernelGGL(motion_partials_kernel<VEC>, dim3((unsigned)nblk), dim3(kThreads), 0, st, v, nbands,
+                                     part));
     SM_CHECK_LAUNCH();
   }
   const int64_t n = (int64_t)B * T;
@@ -331,12 +330,9 @@ extern "C" int sm_gather_frames(const float* clip, int B, int C, int T, int H, i
   const int64_t nblk = (int64_t)n * C * nbands;
   if (nblk > 0x7fffffff) return -2;
   const ClipView v{clip, sB, sC, sT, sH, sW, B, C, T, H, W};
-  if (clip_vec(clip, W, sB, sC, sT, sH, sW) && ((uintptr_t)out & 15) == 0)
-    hipLaunchKernelGGL(gather_frames_kernel<true>, dim3((unsigned)nblk), dim3(kThreads), 0, st, v, nbands, b_idx,
-                       rows_per_b, t_idx, t_fixed, out);
-  else
-    hipLaunchKernelGGL(gather_frames_kernel<false>, dim3((unsigned)nblk), dim3(kThreads), 0, st, v, nbands, b_idx,
-                       rows_per_b, t_idx, t_fixed, out);
+  DISPATCH_BOOL(clip_vec(clip, W, sB, sC, sT, sH, sW) && aligned16(out), VEC,
+                hipLaunchKernelGGL(gather_frames_kernel<VEC>, dim3((unsigned)nblk), dim3(kThreads), 0, st, v, nbands,
+                                   b_idx, rows_per_b, t_idx, t_fixed, out));
   SM_CHECK_LAUNCH();
   return 0;
 }

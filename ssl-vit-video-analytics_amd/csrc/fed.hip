@@ -74,8 +74,6 @@ __global__ void counters_max_kernel(ClientCounters c, int k, int64_t n, int64_t*
   out[i] = m;
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 // ---- multi-tensor exchange: one launch over a cohort's state entries where they live.
 // The table (sm_api.h "FedAvg exchange table") maps every chunk of kChunk elements to a
 // segment (one state entry) and an offset in it; a block takes whole chunks, grid-stride.

@@ -71,18 +71,13 @@ __global__ void __launch_bounds__(256) dp_norms_kernel(ExchangeArgs a, int theta
 // Block c: source c's norm, scale and scaled weight.  stats [2 num_src] = norms, then scales.
 __global__ void __launch_bounds__(256) dp_finalise_kernel(ExchangeArgs a, int64_t C, const double* part,
                                                           float clip_norm, float* stats, float* wsc) {
-  __shared__ double red[256];
   const int j = blockIdx.x, tid = threadIdx.x;
-  double s = 0.0;
-  for (int64_t c = tid; c < C; c += 256) s += part[j * C + c];
-  red[tid] = s;
-  __syncthreads();
+  double s[1] = {0.0};
+  for (int64_t c = tid; c < C; c += 256) s[0] += part[j * C + c];
+  thread_order_sum_d<1, SUM_THREAD0>(s);
   if (tid == 0) {
-    s = 0.0;
-    for (int i = 0; i < 256; ++i) s += red[i];
-    const float norm = (float)sqrt(s);
-    const float q = __fdiv_rn(clip_norm, __fadd_rn(norm, 1e-6f));
-    const float scale = q < 1.f ? q : (q != q ? q : 1.f);   // min(1, q); a NaN stays
+    const float norm = (float)sqrt(s[0]);
+    const float scale = clip_coef(clip_norm, norm);
     stats[j] = norm;
     stats[a.num_src + j] = scale;
     wsc[j] = __fmul_rn(a.w[j], scale);

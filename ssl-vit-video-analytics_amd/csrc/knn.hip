@@ -255,7 +255,6 @@ bool knn_shape_ok(int64_t Nq, int64_t Nb, int k, int splits) {
          splits <= kMaxSplits;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 
 // ---------------------------------------------------------------- knn_vote
@@ -347,10 +346,8 @@ extern "C" int sm_knn_topk(const float* q, int64_t Nq, const float* b, int64_t N
     a.oidx = idx;
   }
   const dim3 grid((unsigned)((Nq + kTQ - 1) / kTQ), (unsigned)s);
-  if (D % 4 == 0 && aligned16(q) && aligned16(b))
-    hipLaunchKernelGGL(knn_topk_kernel<true>, grid, dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL(knn_topk_kernel<false>, grid, dim3(256), 0, st, a);
+  DISPATCH_BOOL(D % 4 == 0 && aligned16(q) && aligned16(b), VEC,
+                hipLaunchKernelGGL(knn_topk_kernel<VEC>, grid, dim3(256), 0, st, a));
   SM_CHECK_LAUNCH();
   if (s > 1) {
     hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((Nq + 3) / 4)), dim3(256), 0, st, a.osim, a.oidx, (int)Nq, k, s,

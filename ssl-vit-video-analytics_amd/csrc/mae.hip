@@ -163,7 +163,6 @@ SM_DEV void token_terms(const LossArgs& a, int64_t tok, int lane, float (&diff)[
 
 template <typename TP>
 __global__ __launch_bounds__(256) void loss_fwd_kernel(LossArgs a, int64_t ntok, int tok_per_block, double* part) {
-  __shared__ double red[2][4];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   double sl = 0.0, sm = 0.0;
   const int64_t t0 = (int64_t)blockIdx.x * tok_per_block;
@@ -178,19 +177,17 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(LossArgs a, int64_t ntok,
     sl += (double)(e * m);
     sm += m;
   }
-  if (lane == 0) { red[0][w] = sl; red[1][w] = sm; }
-  __syncthreads();
+  double v[2] = {sl, sm};   // uniform over the wave: every term came out of a wave_sum
+  waves_sum4_d<2>(v);
   if (threadIdx.x == 0) {
-    part[2 * blockIdx.x] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    part[2 * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    part[2 * blockIdx.x] = v[0];
+    part[2 * blockIdx.x + 1] = v[1];
   }
 }
 
 __global__ void loss_final_kernel(const double* part, int nb, float* loss, float* denom) {
-  double sl = 0.0, sm = 0.0;
-  for (int i = threadIdx.x; i < nb; i += 64) { sl += part[2 * i]; sm += part[2 * i + 1]; }
-  sl = wave_sum_d(sl);
-  sm = wave_sum_d(sm);
+  double sl, sm;
+  sum_pairs_d(part, nb, sl, sm);
   if (threadIdx.x == 0) {
     const float d = (float)sm + 1e-6f;
     denom[0] = d;
@@ -232,29 +229,22 @@ __global__ void gather_rows_kernel(const T* src, const int32_t* idx, int64_t nro
 
 template <typename T>
 __global__ __launch_bounds__(256) void sumsq_kernel(const T* x, int64_t n, double* part) {
-  __shared__ double red[2][4];
-  double s = 0.0, q = 0.0;
+  double sq[2] = {0.0, 0.0};
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const double v = to_f<T>(x[i]);
-    s += v;
-    q += v * v;
+    sq[0] += v;
+    sq[1] += v * v;
   }
-  s = wave_sum_d(s);
-  q = wave_sum_d(q);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[0][w] = s; red[1][w] = q; }
-  __syncthreads();
+  block_sum4_d<2>(sq);
   if (threadIdx.x == 0) {
-    part[2 * blockIdx.x] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    part[2 * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    part[2 * blockIdx.x] = sq[0];
+    part[2 * blockIdx.x + 1] = sq[1];
   }
 }
 
 __global__ void std_final_kernel(const double* part, int nb, int64_t n, float* out) {
-  double s = 0.0, q = 0.0;
-  for (int i = threadIdx.x; i < nb; i += 64) { s += part[2 * i]; q += part[2 * i + 1]; }
-  s = wave_sum_d(s);
-  q = wave_sum_d(q);
+  double s, q;
+  sum_pairs_d(part, nb, s, q);
   if (threadIdx.x == 0) {
     const double mean = s / (double)n;
     double var = (q - s * mean) / (double)(n - 1);
@@ -380,7 +370,7 @@ __global__ void __launch_bounds__(256) adamw_table_nonfinite_kernel(const unsign
     int64_t off, n;
     if (!adamw_chunk_range(t, c, seg, off, n)) continue;
     const float* g = (const float*)t.addr[1 * S + seg] + off;
-    if (((uintptr_t)g & 15u) != 0) {
+    if (!aligned16(g)) {
       for (int64_t i = tid; i < n; i += 256) bad |= !isfinite(g[i]);
       continue;
     }
@@ -500,11 +490,7 @@ __global__ void scale_kernel(float* p, int64_t n, float a) {
     p[i] *= a;
 }
 
-inline int ew_blocks(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b > 8192) b = 8192;
-  return b < 1 ? 1 : (int)b;
-}
+constexpr int kLossTokPerBlock = 256;   // tokens per block of loss_fwd_kernel = per pair of its partials
 
 }  // namespace
 
@@ -523,13 +509,9 @@ extern "C" int sm_pos_blend_fwd(int y_dtype, int x_dtype, const void* y, const f
   if (D % 8) return -2;
   const int64_t n8 = (int64_t)B * T * L * D / 8;
   if (n8 <= 0) return 0;
-#define PB(T1, T2) hipLaunchKernelGGL((pos_blend_fwd_kernel<T1, T2>), dim3(ew_blocks(n8)), dim3(256), 0, st, \
-                                      (const T1*)y, tpos, spos, tok, mask, (T2*)x, T, L, D, n8)
-  if (y_dtype == SM_BF16 && x_dtype == SM_F32) PB(__bf16, float);
-  else if (y_dtype == SM_BF16) PB(__bf16, __bf16);
-  else if (x_dtype == SM_F32) PB(float, float);
-  else PB(float, __bf16);
-#undef PB
+  DISPATCH2(y_dtype, x_dtype,
+            hipLaunchKernelGGL((pos_blend_fwd_kernel<T1, T2>), dim3(ew_grid(n8)), dim3(256), 0, st, (const T1*)y,
+                               tpos, spos, tok, mask, (T2*)x, T, L, D, n8));
   SM_CHECK_LAUNCH();
   return 0;
 }
@@ -541,18 +523,14 @@ extern "C" int sm_pos_blend_bwd(int g_dtype, int y_dtype, const void* dx, const 
   const int F = B * T;
   const int64_t n8 = (int64_t)F * L * D / 8;
   if (n8 <= 0) return 0;
-#define PD(T1, T2) hipLaunchKernelGGL((pos_blend_dy_kernel<T1, T2>), dim3(ew_blocks(n8)), dim3(256), 0, st, \
-                                      (const T1*)dx, mask, (T2*)dy, D, n8)
-  if (g_dtype == SM_F32 && y_dtype == SM_BF16) PD(float, __bf16);
-  else if (g_dtype == SM_F32) PD(float, float);
-  else if (y_dtype == SM_BF16) PD(__bf16, __bf16);
-  else PD(__bf16, float);
-#undef PD
+  DISPATCH2(g_dtype, y_dtype,
+            hipLaunchKernelGGL((pos_blend_dy_kernel<T1, T2>), dim3(ew_grid(n8)), dim3(256), 0, st, (const T1*)dx,
+                               mask, (T2*)dy, D, n8));
   float* pt = ws;
   float* pm = ws + (int64_t)F * D;
   DISPATCH1(g_dtype, hipLaunchKernelGGL(pos_blend_frame_kernel<T>, dim3(F), dim3(128), 0, st, (const T*)dx, mask,
                                         L, D, pt, pm));
-  DISPATCH1(g_dtype, hipLaunchKernelGGL(pos_blend_spos_kernel<T>, dim3(ew_blocks((int64_t)L * D)), dim3(256), 0,
+  DISPATCH1(g_dtype, hipLaunchKernelGGL(pos_blend_spos_kernel<T>, dim3(ew_grid((int64_t)L * D)), dim3(256), 0,
                                         st, (const T*)dx, mask, F, L, D, dspos));
   // dtpos[t][d] += sum_b pt[b][t][d] and dtok[d] += sum_f pm[f][d]: fixed-order fp64 column
   // reductions ([B][T*D] and [F][D] views), many threads per column instead of one
@@ -572,7 +550,7 @@ static LossArgs make_loss_args(const void* pred, const float* clip, int64_t sB, 
 
 extern "C" int64_t sm_loss_workspace_bytes(int B, int T, int L) {
   const int64_t ntok = (int64_t)B * T * L;
-  const int64_t nb = (ntok + 255) / 256;
+  const int64_t nb = (ntok + kLossTokPerBlock - 1) / kLossTokPerBlock;
   return nb * 2 * 8;
 }
 
@@ -582,10 +560,10 @@ extern "C" int sm_mae_loss_fwd(int pred_dtype, const void* pred, const float* cl
   if (H % 8 || W % 8) return -2;
   LossArgs a = make_loss_args(pred, clip, sB, sC, sT, sH, sW, mask, B, T, H, W, norm_pix);
   const int64_t ntok = (int64_t)B * T * a.L;
-  const int tpb = 256;
-  const int nb = (int)((ntok + tpb - 1) / tpb);
+  const int nb = (int)((ntok + kLossTokPerBlock - 1) / kLossTokPerBlock);
   if (ws_bytes < (int64_t)nb * 16) return -4;
-  DISPATCH1(pred_dtype, hipLaunchKernelGGL(loss_fwd_kernel<T>, dim3(nb), dim3(256), 0, st, a, ntok, tpb, (double*)ws));
+  DISPATCH1(pred_dtype, hipLaunchKernelGGL(loss_fwd_kernel<T>, dim3(nb), dim3(256), 0, st, a, ntok, kLossTokPerBlock,
+                                           (double*)ws));
   hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, st, (const double*)ws, nb, loss, denom);
   SM_CHECK_LAUNCH();
   return 0;
@@ -608,7 +586,7 @@ extern "C" int sm_gather_rows(int dtype, const void* src, const int32_t* idx, in
                               hipStream_t st) {
   if (C % 8) return -2;
   if (nrows <= 0) return 0;
-  DISPATCH1(dtype, hipLaunchKernelGGL(gather_rows_kernel<T>, dim3(ew_blocks(nrows * C / 8)), dim3(256), 0, st,
+  DISPATCH1(dtype, hipLaunchKernelGGL(gather_rows_kernel<T>, dim3(ew_grid(nrows * C / 8)), dim3(256), 0, st,
                                       (const T*)src, idx, nrows, C, (T*)dst));
   SM_CHECK_LAUNCH();
   return 0;
@@ -627,7 +605,7 @@ extern "C" int sm_std(int dtype, const void* x, int64_t n, float* out, void* ws,
 }
 
 extern "C" int sm_nonfinite(const float* g, int64_t n, int* flag, hipStream_t st) {
-  hipLaunchKernelGGL(nonfinite_kernel, dim3(ew_blocks(n)), dim3(256), 0, st, g, n, flag);
+  hipLaunchKernelGGL(nonfinite_kernel, dim3(ew_grid(n)), dim3(256), 0, st, g, n, flag);
   SM_CHECK_LAUNCH();
   return 0;
 }
@@ -636,7 +614,7 @@ extern "C" int sm_adamw(float* p, const float* g, float* m, float* v, void* bf16
                         float b1, float b2, float eps, float wd, const int* found_inf, int64_t* step,
                         int advance_step, hipStream_t st) {
   if (n > 0)
-    hipLaunchKernelGGL(adamw_kernel, dim3(ew_blocks(n)), dim3(256), 0, st, p, g, m, v, (__bf16*)bf16_shadow, n, lr,
+    hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid(n)), dim3(256), 0, st, p, g, m, v, (__bf16*)bf16_shadow, n, lr,
                        b1, b2, eps, wd, found_inf, step);
   if (advance_step) hipLaunchKernelGGL(step_incr_kernel, dim3(1), dim3(1), 0, st, found_inf, step);
   SM_CHECK_LAUNCH();
@@ -651,7 +629,7 @@ extern "C" int sm_adamw_table(const void* table, int64_t table_bytes, int64_t nu
   if (num_segments < 0 || num_chunks < 0 || num_segments > (int64_t)1 << 31 || num_chunks > (int64_t)1 << 40) return -2;
   if (num_segments == 0 && num_chunks != 0) return -2;
   const int64_t bytes = ((int64_t)sizeof(SmAdamwTableHeader) + 44 * num_segments + 12 * num_chunks + 15) / 16 * 16;
-  if (!table || ((uintptr_t)table & 15u) != 0 || table_bytes != bytes) return -2;
+  if (!table || !aligned16(table) || table_bytes != bytes) return -2;
   if (num_chunks == 0) return 0;   // no segments, or only empty ones: nothing to launch
   AdamwGroups a{};
   for (int i = 0; i < num_groups; ++i) {
@@ -675,7 +653,7 @@ extern "C" int sm_adamw_table(const void* table, int64_t table_bytes, int64_t nu
 
 extern "C" int sm_fill(float* p, int64_t n, float v, hipStream_t st) {
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(fill_kernel, dim3(ew_blocks(n)), dim3(256), 0, st, p, n, v);
+  hipLaunchKernelGGL(fill_kernel, dim3(ew_grid(n)), dim3(256), 0, st, p, n, v);
   SM_CHECK_LAUNCH();
   return 0;
 }
@@ -686,7 +664,7 @@ extern "C" int sm_patchify(const float* imgs, int B, int C, int T, int H, int W,
   if (p <= 0 || H % p || W % p) return -2;
   const int64_t total = (int64_t)B * C * T * H * W;
   if (total <= 0) return 0;
-  hipLaunchKernelGGL(patchify_kernel, dim3(ew_blocks(total)), dim3(256), 0, st, imgs, sB, sC, sT, sH, sW, B, C, T, H,
+  hipLaunchKernelGGL(patchify_kernel, dim3(ew_grid(total)), dim3(256), 0, st, imgs, sB, sC, sT, sH, sW, B, C, T, H,
                      W, p, out, 0);
   SM_CHECK_LAUNCH();
   return 0;
@@ -699,7 +677,7 @@ extern "C" int sm_unpatchify(const float* tokens, int B, int C, int T, int H, in
   const int64_t total = (int64_t)B * C * T * H * W;
   if (total <= 0) return 0;
   const int64_t sW = 1, sH = W, sT = (int64_t)H * W, sC = (int64_t)T * H * W, sB = (int64_t)C * T * H * W;
-  hipLaunchKernelGGL(patchify_kernel, dim3(ew_blocks(total)), dim3(256), 0, st, tokens, sB, sC, sT, sH, sW, B, C, T,
+  hipLaunchKernelGGL(patchify_kernel, dim3(ew_grid(total)), dim3(256), 0, st, tokens, sB, sC, sT, sH, sW, B, C, T,
                      H, W, p, imgs, 1);
   SM_CHECK_LAUNCH();
   return 0;
@@ -707,7 +685,7 @@ extern "C" int sm_unpatchify(const float* tokens, int B, int C, int T, int H, in
 
 extern "C" int sm_scale(float* p, int64_t n, float a, hipStream_t st) {
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(scale_kernel, dim3(ew_blocks(n)), dim3(256), 0, st, p, n, a);
+  hipLaunchKernelGGL(scale_kernel, dim3(ew_grid(n)), dim3(256), 0, st, p, n, a);
   SM_CHECK_LAUNCH();
   return 0;
 }

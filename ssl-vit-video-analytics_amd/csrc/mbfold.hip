@@ -78,24 +78,17 @@ __global__ __launch_bounds__(256) void mbconv_fold_dw_kernel(int mid, int Cin, d
                                                              const __bf16* W, const float* P, const float* G,
                                                              const float* s, ChanAffine xbn, float* dW) {
   __shared__ float wa[MBF_MAXCIN];   // W[c][i] sc_i
-  __shared__ double red[2][256];
   const int c = blockIdx.x, t = threadIdx.x;
-  double a1 = 0.0, a2 = 0.0;   // sum_i W[c][i] sc_i ss_i,  sum_i W[c][i] sh_i
+  double a[2] = {0.0, 0.0};   // sum_i W[c][i] sc_i ss_i,  sum_i W[c][i] sh_i
   for (int i = t; i < Cin; i += 256) {
     const float w = (float)W[(int64_t)c * Cin + i];
     const float sc = xbn.mean ? xbn.rstd[i] * xbn.w[i] : 1.f;
     wa[i] = w * sc;
-    a1 += (double)wa[i] * (double)s[i];
-    if (xbn.mean) a2 += (double)w * (double)bn_shift(xbn.b[i], xbn.mean[i], sc);
+    a[0] += (double)wa[i] * (double)s[i];
+    if (xbn.mean) a[1] += (double)w * (double)bn_shift(xbn.b[i], xbn.mean[i], sc);
   }
-  red[0][t] = a1;
-  red[1][t] = a2;
-  __syncthreads();
-  a1 = a2 = 0.0;
-  for (int q = 0; q < 256; ++q) {   // fixed order
-    a1 += red[0][q];
-    a2 += red[1][q];
-  }
+  thread_order_sum_d<2, SUM_EVERY_THREAD>(a);   // (its barrier also publishes wa)
+  const double a1 = a[0], a2 = a[1];
   const double om = vec[c], dl = vec[mid + c], cc = vec[2 * mid + c];
   for (int j = t; j < Cin; j += 256) {
     double wg = 0.0;

@@ -688,11 +688,6 @@ __global__ __launch_bounds__(256) void colsum_part_kernel(const T* x, int64_t ld
 }
 
 // ============================================================ launch geometry
-inline int ew_blocks(int64_t n8) {
-  int64_t b = (n8 + 255) / 256;
-  if (b > 8192) b = 8192;
-  return b < 1 ? 1 : (int)b;
-}
 // A block walks a contiguous run of `rpb` rows: about `blocks` blocks, at least `min_rows`
 // rows each, rpb a multiple of `quantum`.
 struct RowSplit {
@@ -962,7 +957,7 @@ extern "C" int sm_gelu_bwd(int pre_dtype, int g_dtype, int64_t n, int ncols, con
   if (n <= 0) return 0;
   if (bad_ew_shape(n, ncols, drop_p)) return -2;
   DISPATCH2(pre_dtype, g_dtype,
-            hipLaunchKernelGGL((gelu_bwd_kernel<T1, T2>), dim3(ew_blocks(n / 8)), dim3(256), 0, st,
+            hipLaunchKernelGGL((gelu_bwd_kernel<T1, T2>), dim3(ew_grid(n / 8)), dim3(256), 0, st,
                                (const T1*)pre, (const T2*)dy, (T2*)dx, n / 8, ncols, drop_p, seed));
   SM_CHECK_LAUNCH();
   return 0;
@@ -973,7 +968,7 @@ extern "C" int sm_add(int a_dtype, int o_dtype, int64_t n, const void* a, const 
   if (n <= 0) return 0;
   if (n % 8) return -2;
   DISPATCH2(a_dtype, o_dtype,
-            hipLaunchKernelGGL((add_kernel<T1, T2, T2>), dim3(ew_blocks(n / 8)), dim3(256), 0, st, (const T1*)a,
+            hipLaunchKernelGGL((add_kernel<T1, T2, T2>), dim3(ew_grid(n / 8)), dim3(256), 0, st, (const T1*)a,
                                (const T2*)b, (T2*)o, n / 8));
   SM_CHECK_LAUNCH();
   return 0;
@@ -983,7 +978,7 @@ extern "C" int sm_cast(int a_dtype, int o_dtype, int64_t n, const void* a, void*
   if (n <= 0) return 0;
   if (n % 8) return -2;
   DISPATCH2(a_dtype, o_dtype,
-            hipLaunchKernelGGL((cast_kernel<T1, T2>), dim3(ew_blocks(n / 8)), dim3(256), 0, st, (const T1*)a,
+            hipLaunchKernelGGL((cast_kernel<T1, T2>), dim3(ew_grid(n / 8)), dim3(256), 0, st, (const T1*)a,
                                (T2*)o, n / 8));
   SM_CHECK_LAUNCH();
   return 0;
@@ -1014,7 +1009,7 @@ extern "C" int sm_gelu_fwd(int dtype, int64_t n, int ncols, const void* x, void*
                            hipStream_t st) {
   if (n <= 0) return 0;
   if (bad_ew_shape(n, ncols, drop_p)) return -2;
-  DISPATCH1(dtype, hipLaunchKernelGGL(gelu_fwd_kernel<T>, dim3(ew_blocks(n / 8)), dim3(256), 0, st, (const T*)x, (T*)y,
+  DISPATCH1(dtype, hipLaunchKernelGGL(gelu_fwd_kernel<T>, dim3(ew_grid(n / 8)), dim3(256), 0, st, (const T*)x, (T*)y,
                                       n / 8, ncols, drop_p, seed));
   SM_CHECK_LAUNCH();
   return 0;
@@ -1025,7 +1020,7 @@ extern "C" int sm_dropout_bwd(int dtype, int64_t n, int ncols, const void* dy, v
   if (n <= 0) return 0;
   if (n % 8 || ncols % 8) return -2;
   const int64_t rpg = rows_per_group > 0 ? rows_per_group : 1;
-  DISPATCH1(dtype, hipLaunchKernelGGL(dropout_bwd_kernel<T>, dim3(ew_blocks(n / 8)), dim3(256), 0, st, (const T*)dy,
+  DISPATCH1(dtype, hipLaunchKernelGGL(dropout_bwd_kernel<T>, dim3(ew_grid(n / 8)), dim3(256), 0, st, (const T*)dy,
                                       (T*)dx, n / 8, ncols, drop_p, seed, row_scale, rpg));
   SM_CHECK_LAUNCH();
   return 0;
@@ -1038,7 +1033,7 @@ extern "C" int sm_cast_dropout_bwd(int64_t n, int ncols, const float* dy, void* 
   if (n <= 0) return 0;
   if (n % 8 || ncols % 8) return -2;
   const int64_t rpg = rows_per_group > 0 ? rows_per_group : 1;
-  hipLaunchKernelGGL((dropout_bwd_kernel<float, __bf16>), dim3(ew_blocks(n / 8)), dim3(256), 0, st, dy,
+  hipLaunchKernelGGL((dropout_bwd_kernel<float, __bf16>), dim3(ew_grid(n / 8)), dim3(256), 0, st, dy,
                      (__bf16*)dx_bf16, n / 8, ncols, drop_p, seed, row_scale, rpg);
   SM_CHECK_LAUNCH();
   return 0;

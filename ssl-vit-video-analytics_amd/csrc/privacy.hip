@@ -197,7 +197,6 @@ __global__ __launch_bounds__(kThreads) void logits_rows_kernel(const float* __re
 // t + 256, ... ascending, then the 256 partials are added in thread order.
 __global__ __launch_bounds__(kThreads) void logits_segments_kernel(const float* __restrict__ rowvals, int64_t N,
                                                                    double* __restrict__ out) {
-  __shared__ double red[kThreads][4];
   const int s = blockIdx.x, tid = threadIdx.x;
   const float* base = rowvals + (int64_t)s * N * 4;
   double a[4] = {0.0, 0.0, 0.0, 0.0};
@@ -206,25 +205,9 @@ __global__ __launch_bounds__(kThreads) void logits_segments_kernel(const float* 
 #pragma unroll
     for (int c = 0; c < 4; ++c) a[c] += (double)q[c];
   }
-#pragma unroll
-  for (int c = 0; c < 4; ++c) red[tid][c] = a[c];
-  __syncthreads();
-  if (tid < 4) {
-    double t = 0.0;
-    for (int i = 0; i < kThreads; ++i) t += red[i][tid];
-    out[(int64_t)s * 4 + tid] = t;
-  }
-}
-
-template <int NG>
-void launch_logits_rows(bool vec, unsigned grid, hipStream_t st, const float* logits, int64_t rows, int C,
-                        const int64_t* labels, int64_t N, int k, float* dlogits, float grad_scale, float* rowvals) {
-  if (vec)
-    hipLaunchKernelGGL((logits_rows_kernel<NG, true>), dim3(grid), dim3(kThreads), 0, st, logits, rows, C, labels, N, k,
-                       dlogits, grad_scale, rowvals);
-  else
-    hipLaunchKernelGGL((logits_rows_kernel<NG, false>), dim3(grid), dim3(kThreads), 0, st, logits, rows, C, labels, N,
-                       k, dlogits, grad_scale, rowvals);
+  static_assert(kThreads == 256, "thread_order_sum_d adds 256 threads' partials");
+  thread_order_sum_d<4, SUM_FIRST_K>(a);               // thread q < 4: column q's sum in a[0]
+  if (tid < 4) out[(int64_t)s * 4 + tid] = a[0];
 }
 
 // ---------------------------------------------------------------- ReLU
@@ -281,8 +264,6 @@ __global__ __launch_bounds__(64) void relu_bias_bwd_kernel(const float* __restri
     if (c0 + j < C) part[(int64_t)blockIdx.y * C + c0 + j] = acc[j];
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int sm_privacy_perturb(const float* z, int64_t N, int D, int G, const float* sigmas,
@@ -300,10 +281,9 @@ extern "C" int sm_privacy_perturb(const float* z, int64_t N, int D, int G, const
     cfg.sigma[g] = sigmas[g];
     cfg.s32[g] = (uint32_t)seeds[g] ^ (uint32_t)(seeds[g] >> 32);      // seed32
   }
-  if (D % 4 == 0 && aligned16(z) && aligned16(out))
-    hipLaunchKernelGGL(perturb_kernel<true>, dim3((unsigned)nblk), dim3(kThreads), 0, st, z, total, D, G, cfg, out);
-  else
-    hipLaunchKernelGGL(perturb_kernel<false>, dim3((unsigned)nblk), dim3(kThreads), 0, st, z, total, D, G, cfg, out);
+  DISPATCH_BOOL(D % 4 == 0 && aligned16(z) && aligned16(out), VEC,
+                hipLaunchKernelGGL(perturb_kernel<VEC>, dim3((unsigned)nblk), dim3(kThreads), 0, st, z, total, D, G, cfg,
+                                   out));
   SM_CHECK_LAUNCH();
   return 0;
 }
@@ -323,12 +303,15 @@ extern "C" int sm_logits_metrics(const float* logits, int64_t rows, int C, const
   if (!ws || ws_bytes < sm_logits_metrics_workspace_bytes(rows) || !aligned16(ws)) return -4;
   float* rowvals = (float*)ws;
   const bool vec = C % 4 == 0 && aligned16(logits) && (!dlogits || aligned16(dlogits));
-  const unsigned grid = (unsigned)nblk;
-  if (C <= 256) launch_logits_rows<1>(vec, grid, st, logits, rows, C, labels, N, k, dlogits, grad_scale, rowvals);
-  else if (C <= 512) launch_logits_rows<2>(vec, grid, st, logits, rows, C, labels, N, k, dlogits, grad_scale, rowvals);
-  else if (C <= 1024) launch_logits_rows<4>(vec, grid, st, logits, rows, C, labels, N, k, dlogits, grad_scale, rowvals);
-  else if (C <= 2048) launch_logits_rows<8>(vec, grid, st, logits, rows, C, labels, N, k, dlogits, grad_scale, rowvals);
-  else launch_logits_rows<16>(vec, grid, st, logits, rows, C, labels, N, k, dlogits, grad_scale, rowvals);
+  DISPATCH_BOOL(vec, VEC, {
+    const auto rows_kernel = C <= 256    ? logits_rows_kernel<1, VEC>
+                             : C <= 512  ? logits_rows_kernel<2, VEC>
+                             : C <= 1024 ? logits_rows_kernel<4, VEC>
+                             : C <= 2048 ? logits_rows_kernel<8, VEC>
+                                         : logits_rows_kernel<16, VEC>;
+    hipLaunchKernelGGL(rows_kernel, dim3((unsigned)nblk), dim3(kThreads), 0, st, logits, rows, C, labels, N, k, dlogits,
+                       grad_scale, rowvals);
+  });
   SM_CHECK_LAUNCH();
   hipLaunchKernelGGL(logits_segments_kernel, dim3((unsigned)S), dim3(kThreads), 0, st, rowvals, N, out);
   SM_CHECK_LAUNCH();
@@ -340,10 +323,8 @@ extern "C" int sm_relu_fwd(const float* pre, int64_t n, float* h, hipStream_t st
   if (!pre || !h) return -2;
   const int64_t nblk = ((n + 3) / 4 + kThreads - 1) / kThreads;
   if (nblk > 0x7fffffff) return -2;
-  if (aligned16(pre) && aligned16(h) && n % 4 == 0)
-    hipLaunchKernelGGL(relu_fwd_kernel<true>, dim3((unsigned)nblk), dim3(kThreads), 0, st, pre, n, h);
-  else
-    hipLaunchKernelGGL(relu_fwd_kernel<false>, dim3((unsigned)nblk), dim3(kThreads), 0, st, pre, n, h);
+  DISPATCH_BOOL(aligned16(pre) && aligned16(h) && n % 4 == 0, VEC,
+                hipLaunchKernelGGL(relu_fwd_kernel<VEC>, dim3((unsigned)nblk), dim3(kThreads), 0, st, pre, n, h));
   SM_CHECK_LAUNCH();
   return 0;
 }
@@ -361,10 +342,8 @@ extern "C" int sm_relu_bias_bwd(const float* dh, const float* h, int64_t M, int 
   if (!ws || ws_bytes < sm_relu_bias_bwd_workspace_bytes(M, C)) return -4;
   float* part = (float*)ws;
   const dim3 grid((unsigned)((C + 255) / 256), (unsigned)nchunks);
-  if (C % 4 == 0 && aligned16(dh) && aligned16(h) && aligned16(dpre))
-    hipLaunchKernelGGL(relu_bias_bwd_kernel<true>, grid, dim3(64), 0, st, dh, h, M, C, dpre, part);
-  else
-    hipLaunchKernelGGL(relu_bias_bwd_kernel<false>, grid, dim3(64), 0, st, dh, h, M, C, dpre, part);
+  DISPATCH_BOOL(C % 4 == 0 && aligned16(dh) && aligned16(h) && aligned16(dpre), VEC,
+                hipLaunchKernelGGL(relu_bias_bwd_kernel<VEC>, grid, dim3(64), 0, st, dh, h, M, C, dpre, part));
   SM_CHECK_LAUNCH();
   colred(part, (int)nchunks, C, nullptr, db, 0, st);
   SM_CHECK_LAUNCH();

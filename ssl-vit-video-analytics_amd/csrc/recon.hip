@@ -166,24 +166,19 @@ __global__ __launch_bounds__(256) void reconstruct_kernel(ReconArgs a, int64_t n
 __global__ __launch_bounds__(256) void clip_metrics_kernel(const float* __restrict__ token_err,
                                                            const uint8_t* __restrict__ mask, int64_t TL,
                                                            float* __restrict__ out) {
-  __shared__ double red[3][256];
   const int tid = threadIdx.x;
   const int64_t t0 = (int64_t)blockIdx.x * TL;
-  double sn = 0.0, sp = 0.0, n = 0.0;
+  double v[3] = {0.0, 0.0, 0.0};                         // sums of the two errors, masked tokens
   for (int64_t i = tid; i < TL; i += 256) {
     if (mask[t0 + i]) {
-      sn += (double)token_err[(t0 + i) * 2];
-      sp += (double)token_err[(t0 + i) * 2 + 1];
-      n += 1.0;
+      v[0] += (double)token_err[(t0 + i) * 2];
+      v[1] += (double)token_err[(t0 + i) * 2 + 1];
+      v[2] += 1.0;
     }
   }
-  red[0][tid] = sn;
-  red[1][tid] = sp;
-  red[2][tid] = n;
-  __syncthreads();
+  thread_order_sum_d<3, SUM_THREAD0>(v);
   if (tid == 0) {
-    sn = sp = n = 0.0;
-    for (int i = 0; i < 256; ++i) { sn += red[0][i]; sp += red[1][i]; n += red[2][i]; }
+    const double sn = v[0], sp = v[1], n = v[2];
     const double en = n > 0.0 ? sn / n : 0.0, mse = n > 0.0 ? sp / n : 0.0;
     float* o = out + (int64_t)blockIdx.x * 4;
     o[0] = (float)en;
@@ -191,14 +186,6 @@ __global__ __launch_bounds__(256) void clip_metrics_kernel(const float* __restri
     o[2] = mse > 0.0 ? (float)(10.0 * log10(1.0 / mse)) : INFINITY;
     o[3] = (float)n;
   }
-}
-
-template <typename TP>
-void launch_reconstruct(bool pack, unsigned grid, hipStream_t st, const ReconArgs& a, int64_t ntok) {
-  if (pack)
-    hipLaunchKernelGGL((reconstruct_kernel<TP, true>), dim3(grid), dim3(256), 0, st, a, ntok);
-  else
-    hipLaunchKernelGGL((reconstruct_kernel<TP, false>), dim3(grid), dim3(256), 0, st, a, ntok);
 }
 
 }  // namespace
@@ -224,10 +211,9 @@ extern "C" int sm_mae_reconstruct(int pred_dtype, const void* pred, const float*
     a.std[c] = std3[s];
   }
   a.panels = panels; a.recon = recon; a.token_err = token_err;
-  const bool pack = ((uintptr_t)panels & 3) == 0;
-  const unsigned grid = (unsigned)nblk;
-  if (pred_dtype == SM_F32) launch_reconstruct<float>(pack, grid, st, a, ntok);
-  else launch_reconstruct<__bf16>(pack, grid, st, a, ntok);
+  DISPATCH_BOOL(((uintptr_t)panels & 3) == 0, PACK,
+                DISPATCH1(pred_dtype, hipLaunchKernelGGL((reconstruct_kernel<T, PACK>), dim3((unsigned)nblk), dim3(256),
+                                                         0, st, a, ntok)));
   SM_CHECK_LAUNCH();
   return 0;
 }

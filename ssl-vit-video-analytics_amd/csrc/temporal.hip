@@ -18,9 +18,6 @@
 
 namespace {
 
-SM_DEV bool dev_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // ------------------------------------------------------------------ masked-frame loss
 // A row of D elements is owned by one wave: lane l holds the groups g = l, l + 64, ... of V
 // consecutive columns (V = 16 bytes of the pred dtype), accumulates over its elements in
@@ -136,7 +133,6 @@ __global__ __launch_bounds__(256) void mfm_final_kernel(const double* __restrict
                                                         const float* __restrict__ rowstat, float w_mfm, float w_var,
                                                         float target_std, float eps, float* __restrict__ colstat,
                                                         float* __restrict__ out) {
-  __shared__ double red[2][256];
   const int tid = threadIdx.x;
   double hs = 0.0, cs = 0.0;
   for (int c = tid; c < D; c += 256) {
@@ -155,13 +151,10 @@ __global__ __launch_bounds__(256) void mfm_final_kernel(const double* __restrict
     colstat[c * 2 + 1] = h > 0.0 ? (float)(-1.0 / ((double)D * (double)N * sigma)) : 0.f;
   }
   for (int i = tid; i < N; i += 256) cs += (double)rowstat[i * 3 + 2];
-  red[0][tid] = hs;
-  red[1][tid] = cs;
-  __syncthreads();
+  double v[2] = {hs, cs};
+  thread_order_sum_d<2, SUM_THREAD0>(v);
   if (tid == 0) {
-    hs = cs = 0.0;
-    for (int i = 0; i < 256; ++i) { hs += red[0][i]; cs += red[1][i]; }
-    const double mfm = 2.0 - 2.0 * cs / N, var = hs / D;
+    const double mfm = 2.0 - 2.0 * v[1] / N, var = v[0] / D;
     out[0] = (float)mfm;
     out[1] = (float)var;
     out[2] = (float)((double)w_mfm * mfm + (double)w_var * var);
@@ -277,43 +270,34 @@ SM_DEV int clip_range_of(const ClipRanges& rg, int b) {
 
 __global__ __launch_bounds__(256) void clip_sumsq_kernel(const float* __restrict__ grad, ClipRanges rg,
                                                          double* __restrict__ part) {
-  __shared__ double red[4];
   const int k = clip_range_of(rg, blockIdx.x);
   const float* g = grad + rg.start[k];
   const int64_t e0 = (int64_t)(blockIdx.x - rg.blk0[k]) * kClipChunk;
   const int64_t e1 = e0 + kClipChunk < rg.len[k] ? e0 + kClipChunk : rg.len[k];
-  const bool vec = dev_aligned16(g);                     // block-uniform (e0 is a multiple of 4)
-  double s = 0.0;
+  const bool vec = aligned16(g);                     // block-uniform (e0 is a multiple of 4)
+  double s[1] = {0.0};
   for (int64_t e = e0 + threadIdx.x * 4; e < e1; e += 1024) {
     float v[4];
     if (vec && e + 4 <= e1) load4(g + e, v);
     else
       for (int j = 0; j < 4; ++j) v[j] = e + j < e1 ? g[e + j] : 0.f;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) s += (double)v[j] * (double)v[j];
+    for (int j = 0; j < 4; ++j) s[0] += (double)v[j] * (double)v[j];
   }
-  s = wave_sum_d(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  block_sum4_d<1>(s);
+  if (threadIdx.x == 0) part[blockIdx.x] = s[0];
 }
 
-// norm = sqrt(sum), coef = min(1, max_norm / (norm + 1e-6)) in fp32 as torch forms it; a NaN norm
-// gives a NaN coefficient (torch's clamp keeps NaN)
+// norm = sqrt(sum), coef = clip_coef(max_norm, norm)
 __global__ __launch_bounds__(256) void clip_final_kernel(const double* __restrict__ part, int nb, float max_norm,
                                                          float* __restrict__ norm_out, float* __restrict__ coef) {
-  __shared__ double red[256];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nb; i += 256) s += part[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
+  double s[1] = {0.0};
+  for (int i = threadIdx.x; i < nb; i += 256) s[0] += part[i];
+  thread_order_sum_d<1, SUM_THREAD0>(s);
   if (threadIdx.x == 0) {
-    s = 0.0;
-    for (int i = 0; i < 256; ++i) s += red[i];
-    const float norm = (float)sqrt(s);
-    const float c = max_norm / (norm + 1e-6f);
+    const float norm = (float)sqrt(s[0]);
     norm_out[0] = norm;
-    coef[0] = c < 1.f ? c : (c != c ? c : 1.f);
+    coef[0] = clip_coef(max_norm, norm);
   }
 }
 
@@ -325,7 +309,7 @@ __global__ __launch_bounds__(256) void clip_scale_kernel(float* __restrict__ gra
   float* g = grad + rg.start[k];
   const int64_t e0 = (int64_t)(blockIdx.x - rg.blk0[k]) * kClipChunk;
   const int64_t e1 = e0 + kClipChunk < rg.len[k] ? e0 + kClipChunk : rg.len[k];
-  const bool vec = dev_aligned16(g);
+  const bool vec = aligned16(g);
   for (int64_t e = e0 + threadIdx.x * 4; e < e1; e += 1024) {
     if (vec && e + 4 <= e1) {
       const f32x4 v = *(const f32x4*)(g + e);
@@ -395,12 +379,6 @@ __global__ __launch_bounds__(256) void relu_dropout_bwd_kernel(const T* __restri
   }
 }
 
-inline unsigned ew_grid(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b > 8192) b = 8192;
-  return b < 1 ? 1u : (unsigned)b;
-}
-
 template <typename T>
 int mfm_fwd(const T* pred, const float* teacher, const int32_t* idx, int R, int N, int D, float w_mfm, float w_var,
             float target_std, float eps, float* out, float* stats, double* part, hipStream_t st) {
@@ -410,13 +388,10 @@ int mfm_fwd(const T* pred, const float* teacher, const int32_t* idx, int R, int 
   float* colstat = stats + (int64_t)N * 3;
   const int nparts = (N + kRowPart - 1) / kRowPart;
   const dim3 rgrid((unsigned)((N + 3) / 4)), cgrid((unsigned)((D + 256 * V - 1) / (256 * V)), (unsigned)nparts);
-  if (vec) {
-    hipLaunchKernelGGL((mfm_row_kernel<T, true>), rgrid, dim3(256), 0, st, pred, teacher, idx, R, N, D, rowstat);
-    hipLaunchKernelGGL((mfm_col_kernel<T, true>), cgrid, dim3(256), 0, st, pred, idx, R, N, D, rowstat, part);
-  } else {
-    hipLaunchKernelGGL((mfm_row_kernel<T, false>), rgrid, dim3(256), 0, st, pred, teacher, idx, R, N, D, rowstat);
-    hipLaunchKernelGGL((mfm_col_kernel<T, false>), cgrid, dim3(256), 0, st, pred, idx, R, N, D, rowstat, part);
-  }
+  DISPATCH_BOOL(vec, VEC, {
+    hipLaunchKernelGGL((mfm_row_kernel<T, VEC>), rgrid, dim3(256), 0, st, pred, teacher, idx, R, N, D, rowstat);
+    hipLaunchKernelGGL((mfm_col_kernel<T, VEC>), cgrid, dim3(256), 0, st, pred, idx, R, N, D, rowstat, part);
+  });
   hipLaunchKernelGGL(mfm_final_kernel, dim3(1), dim3(256), 0, st, part, nparts, N, D, rowstat, w_mfm, w_var,
                      target_std, eps, colstat, out);
   return 0;
@@ -428,12 +403,9 @@ void mfm_bwd(const T* pred, const float* teacher, const int32_t* idx, int R, int
   constexpr int V = Own<T>::V;
   const bool vec = D % V == 0 && aligned16(pred) && aligned16(teacher) && aligned16(dpred);
   const dim3 grid((unsigned)((R + 3) / 4));
-  if (vec)
-    hipLaunchKernelGGL((mfm_bwd_kernel<T, TO, true>), grid, dim3(256), 0, st, pred, teacher, idx, R, N, D, stats,
-                       stats + (int64_t)N * 3, gout, w_mfm, w_var, dpred);
-  else
-    hipLaunchKernelGGL((mfm_bwd_kernel<T, TO, false>), grid, dim3(256), 0, st, pred, teacher, idx, R, N, D, stats,
-                       stats + (int64_t)N * 3, gout, w_mfm, w_var, dpred);
+  DISPATCH_BOOL(vec, VEC,
+                hipLaunchKernelGGL((mfm_bwd_kernel<T, TO, VEC>), grid, dim3(256), 0, st, pred, teacher, idx, R, N, D,
+                                   stats, stats + (int64_t)N * 3, gout, w_mfm, w_var, dpred));
 }
 
 bool mfm_shape_ok(int pred_dtype, int R, int N, int D) {
@@ -453,12 +425,8 @@ extern "C" int sm_mfm_loss_fwd(int pred_dtype, const void* pred, const float* te
                                float* stats, void* ws, int64_t ws_bytes, hipStream_t st) {
   if (!mfm_shape_ok(pred_dtype, R, N, D) || !pred || !teacher || !idx || !out || !stats) return -2;
   if (!ws || ((uintptr_t)ws & 7) || ws_bytes < sm_mfm_loss_workspace_bytes(N, D)) return -4;
-  if (pred_dtype == SM_F32)
-    mfm_fwd<float>((const float*)pred, teacher, idx, R, N, D, w_mfm, w_var, target_std, eps, out, stats, (double*)ws,
-                   st);
-  else
-    mfm_fwd<__bf16>((const __bf16*)pred, teacher, idx, R, N, D, w_mfm, w_var, target_std, eps, out, stats,
-                    (double*)ws, st);
+  DISPATCH1(pred_dtype, mfm_fwd<T>((const T*)pred, teacher, idx, R, N, D, w_mfm, w_var, target_std, eps, out, stats,
+                                   (double*)ws, st));
   SM_CHECK_LAUNCH();
   return 0;
 }
@@ -469,16 +437,8 @@ extern "C" int sm_mfm_loss_bwd(int pred_dtype, int dpred_dtype, const void* pred
   if (!mfm_shape_ok(pred_dtype, R, N, D) || (dpred_dtype != SM_F32 && dpred_dtype != SM_BF16) || !pred || !teacher ||
       !idx || !stats || !grad_out || !dpred)
     return -2;
-#define MFM_BWD(T, TO) \
-  mfm_bwd<T, TO>((const T*)pred, teacher, idx, R, N, D, stats, grad_out, w_mfm, w_var, (TO*)dpred, st)
-  if (pred_dtype == SM_F32) {
-    if (dpred_dtype == SM_F32) MFM_BWD(float, float);
-    else MFM_BWD(float, __bf16);
-  } else {
-    if (dpred_dtype == SM_F32) MFM_BWD(__bf16, float);
-    else MFM_BWD(__bf16, __bf16);
-  }
-#undef MFM_BWD
+  DISPATCH2(pred_dtype, dpred_dtype, mfm_bwd<T1, T2>((const T1*)pred, teacher, idx, R, N, D, stats, grad_out, w_mfm,
+                                                     w_var, (T2*)dpred, st));
   SM_CHECK_LAUNCH();
   return 0;
 }
@@ -487,10 +447,9 @@ extern "C" int sm_ema_update(float* dst, const float* src, int64_t n, float mf, 
   if (n < 0) return -2;
   if (n == 0) return 0;
   if (!dst || !src) return -2;
-  if (aligned16(dst) && aligned16(src))
-    hipLaunchKernelGGL(ema_kernel<true>, dim3(ew_grid((n + 3) / 4)), dim3(256), 0, st, dst, src, n, mf, af);
-  else
-    hipLaunchKernelGGL(ema_kernel<false>, dim3(ew_grid(n)), dim3(256), 0, st, dst, src, n, mf, af);
+  DISPATCH_BOOL(aligned16(dst) && aligned16(src), VEC,
+                hipLaunchKernelGGL(ema_kernel<VEC>, dim3(ew_grid(VEC ? (n + 3) / 4 : n)), dim3(256), 0, st, dst, src,
+                                   n, mf, af));
   SM_CHECK_LAUNCH();
   return 0;
 }
@@ -548,12 +507,8 @@ extern "C" int sm_relu_dropout_fwd(int dtype, int64_t n, int ncols, const void* 
     return -2;
   if (n == 0) return 0;
   if (!x || !y || !aligned16(x) || !aligned16(y)) return -2;
-  if (dtype == SM_BF16)
-    hipLaunchKernelGGL(relu_dropout_fwd_kernel<__bf16>, dim3(ew_grid(n / 8)), dim3(256), 0, st, (const __bf16*)x,
-                       (__bf16*)y, n / 8, ncols, drop_p, seed);
-  else
-    hipLaunchKernelGGL(relu_dropout_fwd_kernel<float>, dim3(ew_grid(n / 8)), dim3(256), 0, st, (const float*)x,
-                       (float*)y, n / 8, ncols, drop_p, seed);
+  DISPATCH1(dtype, hipLaunchKernelGGL(relu_dropout_fwd_kernel<T>, dim3(ew_grid(n / 8)), dim3(256), 0, st,
+                                      (const T*)x, (T*)y, n / 8, ncols, drop_p, seed));
   SM_CHECK_LAUNCH();
   return 0;
 }
@@ -565,12 +520,8 @@ extern "C" int sm_relu_dropout_bwd(int dtype, int64_t n, int ncols, const void* 
     return -2;
   if (n == 0) return 0;
   if (!ref || !dy || !dx || !aligned16(ref) || !aligned16(dy) || !aligned16(dx)) return -2;
-  if (dtype == SM_BF16)
-    hipLaunchKernelGGL(relu_dropout_bwd_kernel<__bf16>, dim3(ew_grid(n / 8)), dim3(256), 0, st, (const __bf16*)ref,
-                       (const __bf16*)dy, (__bf16*)dx, n / 8, ncols, drop_p, seed);
-  else
-    hipLaunchKernelGGL(relu_dropout_bwd_kernel<float>, dim3(ew_grid(n / 8)), dim3(256), 0, st, (const float*)ref,
-                       (const float*)dy, (float*)dx, n / 8, ncols, drop_p, seed);
+  DISPATCH1(dtype, hipLaunchKernelGGL(relu_dropout_bwd_kernel<T>, dim3(ew_grid(n / 8)), dim3(256), 0, st,
+                                      (const T*)ref, (const T*)dy, (T*)dx, n / 8, ncols, drop_p, seed));
   SM_CHECK_LAUNCH();
   return 0;
 }

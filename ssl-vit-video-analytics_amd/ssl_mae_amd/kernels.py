@@ -460,22 +460,28 @@ def fill_(t, v):
 
 
 # ------------------------------------------------------------------ convolutions
+def _stem_geometry(clip):
+    """B, T, H, W, the five element strides (sB, sC, sT, sH, sW) and the stride-2, pad-1 output
+    size of a clip [B,3,T,H,W] or of frames [N,3,H,W] (T = 1, sT = 0)."""
+    if clip.dim() == 5:
+        B, _, T, H, W = clip.shape
+        strides = clip.stride()
+    else:
+        B, _, H, W = clip.shape
+        T = 1
+        sB, sC, sH, sW = clip.stride()
+        strides = (sB, sC, 0, sH, sW)
+    return B, T, H, W, strides, (H + 1) // 2, (W + 1) // 2
+
+
 def stem_im2col(clip, out_dtype, frames_view=None):
     """clip [B,3,T,H,W] (fp32, any strides) -> col [B*T*Ho*Wo, 32] (stride 2, pad 1)."""
     _chk(clip)
     if clip.dtype != torch.float32:
         clip = clip.float()
-    if clip.dim() == 5:
-        B, C, T, H, W = clip.shape
-        sB, sC, sT, sH, sW = clip.stride()
-    else:  # frames [N,3,H,W]
-        B, C, H, W = clip.shape
-        T = 1
-        sB, sC, sH, sW = clip.stride()
-        sT = 0
-    Ho, Wo = (H + 1) // 2, (W + 1) // 2
+    B, T, H, W, strides, Ho, Wo = _stem_geometry(clip)
     col = torch.empty((B * T * Ho * Wo, 32), dtype=out_dtype, device=clip.device)
-    call("sm_stem_im2col", dt(col), ptr(clip), B, T, H, W, sB, sC, sT, sH, sW, 2, ptr(col), stream())
+    call("sm_stem_im2col", dt(col), ptr(clip), B, T, H, W, *strides, 2, ptr(col), stream())
     return col, (B * T, Ho, Wo)
 
 
@@ -490,22 +496,14 @@ def stem_conv1_bn_stats(clip, wpack, running_mean=None, running_var=None, moment
         clip = clip.float()
     if wpack.dtype != torch.bfloat16 or tuple(wpack.shape) != (48, 32) or not wpack.is_contiguous():
         raise _lib.KernelError("stem_conv1_bn_stats: wpack is contiguous bf16 [48][32]")
-    if clip.dim() == 5:
-        B, C, T, H, W = clip.shape
-        sB, sC, sT, sH, sW = clip.stride()
-    else:  # frames [N,3,H,W]
-        B, C, H, W = clip.shape
-        T = 1
-        sB, sC, sH, sW = clip.stride()
-        sT = 0
-    Ho, Wo = (H + 1) // 2, (W + 1) // 2
+    B, T, H, W, strides, Ho, Wo = _stem_geometry(clip)
     y = torch.empty((B * T * Ho * Wo, 48), dtype=torch.bfloat16, device=clip.device)
     mean = torch.empty(48, dtype=torch.float32, device=clip.device)
     rstd = torch.empty(48, dtype=torch.float32, device=clip.device)
     nbytes = query("sm_stem_conv1_workspace_bytes")
     ws = _ws(nbytes, clip.device)
-    call("sm_stem_conv1_bn_stats", ptr(clip), B, T, H, W, sB, sC, sT, sH, sW, ptr(wpack), ptr(y), ptr(mean),
-         ptr(rstd), ptr(running_mean), ptr(running_var), ptr(num_batches), float(momentum), float(eps), int(updates),
+    call("sm_stem_conv1_bn_stats", ptr(clip), B, T, H, W, *strides, ptr(wpack), ptr(y), ptr(mean), ptr(rstd),
+         ptr(running_mean), ptr(running_var), ptr(num_batches), float(momentum), float(eps), int(updates),
          ptr(ws), nbytes, stream())
     return y, mean, rstd, (B * T, Ho, Wo)
 

@@ -109,6 +109,30 @@ def test_norms_and_scales(k):
     assert np.array_equal(again.view(np.int32), stats.view(np.int32))
 
 
+@pytest.mark.parametrize("n", [5, 256 * 2048 + 1], ids=["1chunk", "257chunks"])
+def test_norms_over_1_and_257_chunks(n):
+    """One clipped segment of 1 chunk and of 257 chunks: the finalise block's 256 strided sums hold one
+    partial in thread 0 only, and two in thread 0 next to one in every other thread.  The checks of
+    test_norms_and_scales, and the update against the mirror bit for bit."""
+    from ssl_mae_amd import federated as F
+    from ssl_mae_amd import kernels as K
+    k, lens, modes = 2, (n,), (1,)
+    theta, sources, _, w, norms64 = _case(k, lens, modes)
+    models = _device(theta, sources, lens)
+    table, _ = K.fedavg_exchange_table(models, torch.float32)
+    chunks = -(-n // 2048)
+    stats = K.fedavg_dp_exchange([1, 2], w, 0, [0], table, chunks, _seg_clip(modes), CLIP, 0.0, 1).cpu().numpy()
+    norms, scales = stats[:k], stats[k:]
+    rel = np.abs(norms.astype(np.float64) - norms64) / norms64
+    print(f"{chunks} chunks: largest relative norm error {rel.max():.3e}")
+    assert np.all(rel <= 1e-5)
+    want = np.minimum(np.float32(1.0), np.float32(CLIP) / (norms + np.float32(1e-6)))
+    assert want.dtype == np.float32 and np.array_equal(scales.view(np.int32), want.view(np.int32))
+    assert np.array_equal(scales < 1.0, norms64 > CLIP)
+    mirror, _ = F.dp_aggregate_mirror(theta, sources, w, modes, CLIP, scales=scales)
+    assert np.array_equal(_bits(models[0][0]), mirror[0].view(np.int32))
+
+
 @pytest.mark.parametrize("k", K_VALUES)
 def test_update_without_noise_is_the_mirror(k):
     from oracle import fedavg_oracle as O

@@ -757,6 +757,51 @@ def test_mae_loss(dtype):
     assert rel_err(dpred, pr.grad) < (1e-5 if dtype == torch.float32 else 1e-2)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("B,T,H,W", [(1, 3, 8, 24), (3, 5, 24, 24), (1, 29, 24, 24)])
+def test_mae_loss_partial_blocks(B, T, H, W, dtype):
+    """9, 135 and 261 tokens, none a multiple of 4: one block whose four waves take 3, 2, 2, 2 tokens,
+    one with a partly filled last group of four, and a second block of 5 tokens."""
+    from oracle import mae_oracle as O
+    L = (H // 8) * (W // 8)
+    clip = rnd(B, 3, T, H, W, seed=102)
+    torch.manual_seed(4)
+    mask = O.get_tube_mask(B, T, L, 0.75)
+    pred = rnd(B, T * L, 192, dtype=dtype, seed=103)
+    pr = pred.float().requires_grad_(True)
+    lr_ = O.masked_mse(pr, O.norm_pix(O.patchify(clip, 8)), mask)
+    lr_.backward()
+    kk = KK()
+    m8 = mask.to(torch.uint8).to(DEV)
+    loss, denom = kk.mae_loss_fwd(pred.to(DEV), clip.to(DEV), m8)
+    assert abs(loss.item() - lr_.item()) < 1e-5 * max(1, abs(lr_.item()))
+    assert denom.item() == pytest.approx(float(mask.sum()) + 1e-6, rel=1e-6)
+    dpred = kk.mae_loss_bwd(pred.to(DEV), clip.to(DEV), m8, True, torch.ones((), device=DEV), denom)
+    assert rel_err(dpred, pr.grad) < (1e-5 if dtype == torch.float32 else 1e-2)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("n", [2, 257])
+def test_std_of_a_few_elements(n, dtype):
+    """n = 2: one wave holds both terms; n = 257: block 0's four waves are full and block 1 holds one term."""
+    x = rnd(n, dtype=dtype, seed=120 + n)
+    sd = KK().std(x.to(DEV))
+    assert abs(sd.item() - x.float().std().item()) < 1e-4
+
+
+def test_fill_and_scale_past_the_grid_cap():
+    """n = 8192 * 256 + 1: the grid is capped at 8192 blocks and the grid-stride loop's second turn is
+    one element."""
+    n = 8192 * 256 + 1
+    t = torch.empty(n, device=DEV)
+    KK().fill_(t, 1.5)
+    assert bool((t == 1.5).all())
+    x = rnd(n, seed=121)
+    d = x.to(DEV)
+    KK().scale_(d, 0.75)
+    assert torch.equal(d.cpu(), x * 0.75)
+
+
 def test_pos_blend():
     B, T, L, D = 2, 3, 16, 384
     y = rnd(B * T * L, D, dtype=torch.bfloat16, seed=110)

@@ -131,6 +131,36 @@ def test_folded_expand_gradients_vs_fp32_and_two_pass(Fr, H, Cin, mid, s, bnin):
     assert (diff == 0).float().mean().item() > 0.99
 
 
+@pytest.mark.parametrize("Cin", [16, 264])
+def test_fold_dw_vs_torch_formula(Cin):
+    """sm_mbconv_fold_dw with a BatchNorm-folded input against the fp64 torch formula, fp32 output
+    within 1e-5 (max-norm relative, as the prep kernel's): Cin = 16 leaves 240 of the block's 256
+    partial sums of a1 / a2 empty, Cin = 264 gives threads 0..7 two terms each."""
+    kk = KK()
+    mid, M = 8, 1000
+    w = rnd(mid, Cin, seed=340, scale=1.5 / Cin ** 0.5).to(torch.bfloat16).to(DEV)
+    vec = torch.stack([rnd(mid, seed=341, scale=0.2) + 1.0, rnd(mid, seed=342, scale=1e-3),
+                       rnd(mid, seed=343, scale=1e-3)]).to(DEV)
+    P = rnd(mid, Cin, seed=344).to(DEV)
+    xs = rnd(M, Cin, seed=345).double() + 0.2
+    G, s = (xs.t() @ xs).float().to(DEV), xs.sum(0).float().to(DEV)
+    xbn = _xbn(Cin, 350)
+    sink0 = rnd(mid, Cin, seed=346).to(DEV)
+    got = kk.mbconv_fold_dw(vec, w, P, G, s, M, sink0.clone(), xbn)
+    torch.cuda.synchronize()
+    sc = (xbn[1] * xbn[2]).double()
+    sh = xbn[3].double() - xbn[0].double() * sc
+    Wd, om, dl, cc = w.double(), vec[0].double(), vec[1].double(), vec[2].double()
+    wa = (w.float() * (xbn[1] * xbn[2])).double()                    # W sc, rounded to fp32 as the kernel stores it
+    a1, a2 = wa @ s.double(), Wd @ sh
+    sj = sc * s.double() + M * sh
+    wg = sc * (wa @ G.double()) + a1[:, None] * sh + a2[:, None] * sj
+    ref = sink0.double() + om[:, None] * P.double() + cc[:, None] * sj - dl[:, None] * wg
+    err = rel_err(got, ref)
+    print(f"fold_dw Cin={Cin}: err {err:.3e}")
+    assert err < 1e-5
+
+
 # ------------------------------------------------------------------ 2. prep kernel
 @pytest.mark.parametrize("mid,Cin,bnin", [(64, 16, False), (384, 96, False), (64, 16, True), (384, 96, True)])
 def test_fold_prep_vs_torch_formula(mid, Cin, bnin):

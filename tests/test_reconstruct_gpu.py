@@ -148,6 +148,30 @@ def test_constant_patch(dtype):
     assert float((patch - want).abs().max()) < 5e-3 * 0.3 and float(patch.std()) > 0
 
 
+@pytest.mark.parametrize("T,L", [(1, 1), (3, 85), (1, 257)], ids=["TL1", "TL255", "TL257"])
+def test_clip_metrics_token_counts(T, L):
+    """sm_recon_clip_metrics on its own over T L = 1, 255 and 257 tokens per clip (a block's 256 strided
+    sums hold one term, one term in all but the last thread, and two terms in thread 0) against the
+    mirror's fp64 masked means, to the 1e-5 of _check; clip 0 all masked, clip 1 about half."""
+    from ssl_mae_amd import ops
+    B = 2
+    g = torch.Generator().manual_seed(T * 1000 + L)
+    te = torch.rand(B * T * L, 2, generator=g) * 0.5 + 0.01        # pixel error <= 0.51: PSNR >= 2.9 dB, away from 0
+    mask = torch.ones(B, T, L, dtype=torch.uint8)
+    mask[1] = (torch.rand(T, L, generator=g) < 0.5).to(torch.uint8)
+    mask[1, 0, 0] = 1
+    cm = ops.recon_clip_metrics(te.to(DEV), mask.to(DEV)).double().cpu()
+    err, m = te.double().reshape(B, T * L, 2), mask.reshape(B, T * L).bool()
+    for b in range(B):
+        n = int(m[b].sum())
+        en, mse = float(err[b, m[b], 0].sum() / n), float(err[b, m[b], 1].sum() / n)
+        want = (en, mse, 10.0 * np.log10(1.0 / mse))
+        print(f"T L = {T * L}, clip {b}: n {n}, got {cm[b].tolist()}, want {want}")
+        assert float(cm[b, 3]) == n
+        for j in range(3):
+            assert abs(float(cm[b, j]) - want[j]) <= 1e-5 * abs(want[j]), (b, j)
+
+
 def test_pixel_error_zero_gives_infinite_psnr():
     """norm_pix off and pred = patchify(clip): both errors are exactly 0 on masked tokens."""
     _, clip, mask = _inputs(SHAPES[2], mask_kind="ones", seed=4)

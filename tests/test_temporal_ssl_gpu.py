@@ -50,6 +50,9 @@ def gold(golden_dir):
 
 # ------------------------------------------------------------------ masked-frame loss
 MFM_CASES = [(8, 576, 6), (15, 37, 11), (4, 64, 1), (400, 96, 300)]     # (R, D, N); 300 rows = 10 partitions of 32
+# the final kernel's 256 strided sums over N rows and D columns see fewer than 256, and more than 256, of each
+# (N = 33: two row partitions); D = 4 and 100 take the scalar form in bf16 (no multiple of 8)
+MFM_CASES += [(N + 3, D, N) for N in (1, 33, 257) for D in (4, 100, 576)]
 W_MFM, W_VAR, EPS, UP = 1.0, 25.0, 1e-4, 0.7
 _mfm_ref = {}
 
@@ -159,6 +162,22 @@ def test_ema_update(m, offset):
     assert torch.equal(src.cpu(), p)
 
 
+@pytest.mark.parametrize("offset", [0, 1])
+def test_ema_update_past_the_grid_cap(offset):
+    """n = 4 * 8192 * 256 + 5: the grid is capped at 8192 blocks, so the 16-byte form's grid-stride loop
+    takes a second turn (one group) and a tail of one element; the scalar form (offset view) takes five."""
+    n = 4 * 8192 * 256 + 5
+    g = torch.Generator().manual_seed(6)
+    e = torch.randn(n + offset, generator=g)[offset:]
+    p = torch.randn(n + offset, generator=g)[offset:]
+    ref, bound = TM.ema_fp64(e, p, 0.996)
+    dst = torch.empty(n + offset, device=DEV)[offset:]
+    dst.copy_(e)
+    assert (dst.data_ptr() % 16 != 0) == bool(offset)
+    KK().ema_update(dst, p.to(DEV), 0.996)
+    assert bool(((dst.cpu().double() - ref).abs() <= bound).all())
+
+
 def test_update_ema_over_the_flat_buffers():
     model = TS.TemporalSSL(64, 1, 2, 5, encoder=TM.StandInEncoder(64)).to(DEV)
     ema = copy.deepcopy(model)
@@ -208,6 +227,36 @@ def test_grad_clip(ranges):
     d2 = g.to(DEV)
     n2 = KK().grad_clip(d2, ranges, 1.0)
     assert torch.equal(d2.view(torch.int32), d.view(torch.int32)) and torch.equal(n2, norm_out)
+
+
+_CLIP_EDGE_N = 256 * 8192 + 1
+
+
+@pytest.fixture(scope="module")
+def clip_edge_grad():
+    return torch.randn(_CLIP_EDGE_N + 8, generator=torch.Generator().manual_seed(12)) * 0.3
+
+
+@pytest.mark.parametrize("start", [0, 3], ids=["aligned", "misaligned"])
+@pytest.mark.parametrize("length", [1, 8192, 8192 + 1, 256 * 8192, _CLIP_EDGE_N])
+def test_grad_clip_chunk_counts(clip_edge_grad, length, start):
+    """One range of 1, 256 and 257 chunks (the second level's 256 strided sums see fewer than 256,
+    exactly 256 and 257 partials), and chunks of one element and of 8192 + 1 (a block whose last
+    three waves, or all but one lane, add nothing)."""
+    g = clip_edge_grad
+    ranges = [(start, start + length)]
+    max_norm = 0.01                                          # below |g[0]| = 0.04 and |g[3]| = 0.14: every case clips
+    d = g.to(DEV)
+    norm_out = KK().grad_clip(d, ranges, max_norm)
+    norm, coef = _clip_ref(g, ranges, max_norm, norm_out)
+    print("length", length, "norm", float(norm_out), norm, "coef", coef)
+    assert abs(float(norm_out) - norm) <= 1e-6 * norm and coef < 1.0
+    got = d.cpu()
+    inside = torch.zeros(g.numel(), dtype=torch.bool)
+    inside[start:start + length] = True
+    assert torch.equal(got[~inside].view(torch.int32), g[~inside].view(torch.int32))
+    want = g[inside].double() * coef
+    assert bool(((got[inside].double() - want).abs() <= 2.0 ** -23 * want.abs()).all())
 
 
 def test_grad_clip_below_max_norm_leaves_the_buffer():
