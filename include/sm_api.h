@@ -793,6 +793,67 @@ int sm_frames_crop_resize_normalize(const uint8_t* packed, const int64_t* desc, 
                                     int Ho, int Wo, const float* mean3, const float* std3, int bgr_swap, float* out,
                                     hipStream_t st);
 
+/* ---- visual privacy (csrc/anonymize.hip; the anonymisation half of the reference's
+ * src/run_privacy.py:118-226 run_visual_privacy: cv2.GaussianBlur over detected boxes.  The detector
+ * is not part of this build: the boxes are an input).  One kernel launch each (the statistics after
+ * a memset of their output on the same stream), no workspace, no host sync.
+ *
+ * packed uint8: frame n is [H_n][W_n][3] (RGB, HWC) starting at byte desc[n][0]; desc int64 [N][3]
+ * (DEVICE) = {byte offset, H, W}; frames of one call may differ in size, offsets need no alignment.
+ * boxes int32 [num_boxes][4] (DEVICE) = {x, y, w, h}; box_start int32 [N + 1] (DEVICE): frame n
+ * owns boxes [box_start[n], box_start[n + 1]).  max_h / max_w are host upper bounds on the frame
+ * sizes of the call: the grid is N x ceil(max_h / SM_BOX_TILE_H) x ceil(max_w / SM_BOX_TILE_W)
+ * blocks, so the host never reads desc back.
+ *
+ * Validity is decided in the kernel; nothing outside packed, boxes or box_start is read.  A frame
+ * is skipped (its bytes of `out` are not written, its stats row is zeros) when H or W is outside
+ * [1, 8192], when H > max_h or W > max_w, or when its byte range leaves [0, packed_bytes).  The ends
+ * of a box range are clamped into [0, num_boxes]; a reversed range is empty.  A box is clipped to
+ * its frame, x0 = max(x, 0), x1 = min(x + w, W), likewise y, the sums in 64 bits; it is empty when
+ * w <= 0, h <= 0 or nothing remains.  (The reference's numpy slice img[y:y+h, x:x+w] drops a box
+ * that starts at a negative coordinate; this build clips it.)
+ *
+ * sm_frames_box_blur: with U the union of a frame's clipped boxes, a pixel outside U keeps its
+ * input bytes; a pixel in U gets, per channel, the separable Gaussian of the ORIGINAL frame.
+ * weights is a HOST array of ksize floats, ksize odd in [3, 63], r = (ksize - 1) / 2.  refl(i, n) is
+ * the reflect-101 index (no edge repetition), periodic and so defined for n <= r too: 0 for
+ * n == 1; otherwise p = 2 (n - 1), i = i mod p (non-negative), and i >= n maps to p - i.
+ *   h(y, x) = acc after acc = acc + weights[i] * fp32(u[y][refl(x + i - r, W)]) for i = 0 .. ksize - 1
+ *             ascending from acc = 0, every product and every sum rounded to fp32 on its own (no fma)
+ *   v(y, x) = the same over weights[i] * h(refl(y + i - r, H), x)
+ *   out     = (uint8) min(255, max(0, rintf(v))), round-half-even
+ * A pixel has one summation order: the result does not depend on the tiling, on the number of
+ * boxes, their order or their overlap, and two calls give the same bits.  For one box this is
+ * cv2.GaussianBlur(roi, (k, k), 0) on a ROI view in exact arithmetic (OpenCV too reads the parent
+ * image beyond the ROI and reflects only at the frame's edge).  Two documented deviations from the
+ * reference: its sequential loop blurs already-blurred pixels where two boxes lie closer than r,
+ * this does not; and OpenCV's 8-bit path is fixed-point: agreement within one grey level is
+ * expected but NOT MEASURED (no OpenCV where this was built).
+ *
+ * sm_box_region_stats: a and b are two buffers of the layout above (packed_bytes each, one desc).
+ * stats int64 [N][4] = {P, SSE, Ea, Eb} per frame: P = pixels in U; SSE = sum over U and 3
+ * channels of (a - b)^2; E_img = sum over pixels (y, x) in U and 3 channels of
+ * [x + 1 < W] (img[y][x+1] - img[y][x])^2 + [y + 1 < H] (img[y+1][x] - img[y][x])^2 (a neighbour may
+ * lie outside U); Ea = E_a, Eb = E_b.  All exact integers (64-bit atomics, the order is free); the
+ * call zeroes stats itself, on the stream.
+ *
+ * Both return 0 (also for N == 0, nothing launched), -2 with nothing launched for N < 0, N x the
+ * tile counts above 2^31 - 1 blocks, max_h or max_w outside [1, 8192], an even ksize or one outside
+ * [3, 63], num_boxes < 0, packed_bytes < 0 and, for N > 0, a null pointer (boxes may be null when
+ * num_boxes == 0) or an `out` whose packed_bytes overlap those of `packed` (the blur reads halos of
+ * the original frame while other blocks write: the buffers must be disjoint); otherwise the
+ * hipError_t of the launch.  Every thread of a tile walks all of its frame's boxes (twice where the
+ * tile meets one), the copy tiles included: the cost per tile is linear in the boxes per frame, meant
+ * for a few boxes per frame, not for dense box files.  With num_boxes == 0 the launch reserves no LDS. */
+#define SM_BOX_TILE_H 32
+#define SM_BOX_TILE_W 64
+int sm_frames_box_blur(const uint8_t* packed, const int64_t* desc, int64_t packed_bytes, int N, int max_h, int max_w,
+                       const int32_t* boxes, const int32_t* box_start, int64_t num_boxes, const float* weights,
+                       int ksize, uint8_t* out, hipStream_t st);
+int sm_box_region_stats(const uint8_t* a, const uint8_t* b, const int64_t* desc, int64_t packed_bytes, int N, int max_h,
+                        int max_w, const int32_t* boxes, const int32_t* box_start, int64_t num_boxes, int64_t* stats,
+                        hipStream_t st);
+
 /* ---- box calibration (bench.py; csrc/calib.hip): `blocks` workgroups of 4 waves, each wave
  * `iters` x 8 v_mfma_f32_32x32x16_bf16 (shape 32) or the same FLOPs as 16
  * v_mfma_f32_16x16x32_bf16 (shape 16) on random register operands.  stamps [blocks][2] int64:

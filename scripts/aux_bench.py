@@ -37,6 +37,10 @@
   against sm_frames_resize_normalize on the full frames and against the same crop in eager torch
   ops, alternating, and the 4.9 GB copy calibration (see `crop`).
 
+* `aux_bench.py blur [--out profiles/box_blur.txt]`: the box blur (sm_frames_box_blur) at k = 15, 31,
+  51 on 2048 frames with and without boxes, against a plain device copy of the same bytes and the
+  same result in eager torch ops, the statistics launch, and the 4.9 GB copy calibration (see `blur`).
+
 Prints one JSON line per kernel; run under rocprofv3 --kernel-trace --stats to
 cross-check the average launch durations."""
 import json
@@ -804,11 +808,115 @@ def knn(out_path=None, rounds=5, D=576, num_classes=101, temperature=0.07):
             f.write(text)
 
 
+def blur(out_path=None, N=2048, reps=10, rounds=5):
+    """sm_frames_box_blur at k = 15, 31, 51 on 2048 frames of 240x320 with one 96x96 box each, the
+    same frames with no boxes (the launch then reserves no LDS) and with one box in frame 0 only (the
+    same copy work under the blur tiles' LDS reservation), and 2048 frames of 112^2 with one 48x48 box; alternating in every
+    round with a plain device copy of the same bytes (out.copy_(packed)) and with the same result
+    from eager torch ops on the device (fp32 frames, reflect padding, separable conv2d, torch.where
+    on a box mask, round, to uint8).  GB/s over bytes read plus written (2 x the packed bytes).  The
+    statistics launch (memset + sm_box_region_stats) is timed as well.  Ends with the 4.9 GB copy
+    calibration.  No target is asserted: what is measured is written down.  Agreement with
+    OpenCV's own 8-bit GaussianBlur is NOT measured (no OpenCV here)."""
+    import statistics
+    import torch.nn.functional as Fn
+    from ssl_mae_amd.visual_privacy import gaussian_weights
+    dev = torch.device("cuda")
+    lines = [f"device: {torch.cuda.get_device_name(0)}; N={N} frames; {rounds} rounds of {reps} launches, alternating, "
+             "median [min .. max]; GB = bytes read + written = 2 x packed bytes"]
+    print(lines[0], flush=True)
+
+    def emit(line):                                     # every line as it is measured: a long run shows progress
+        lines.append(line)
+        print(line, flush=True)
+
+    g = torch.Generator(device="cuda").manual_seed(0)
+    # boxed: how many of the N frames own a box.  0 boxes: the launch reserves no LDS; 1 box (frame 0): the
+    # same copy work with the blur tiles' LDS reserved, which isolates what that reservation costs the copy tiles
+    for H, W, bs, boxed in ((240, 320, 96, N), (240, 320, 96, 0), (240, 320, 96, 1), (112, 112, 48, N)):
+        src = torch.randint(0, 256, (N, H, W, 3), dtype=torch.uint8, device=dev, generator=g)
+        packed = src.view(-1)
+        out = torch.empty_like(packed)
+        out2 = torch.empty_like(packed)
+        desc = torch.tensor([[n * H * W * 3, H, W] for n in range(N)], device=dev)
+        xy = [((37 * n) % (W - bs), (23 * n) % (H - bs)) for n in range(N)]
+        xy = xy[:boxed]
+        boxes = torch.tensor([[x, y, bs, bs] for x, y in xy], dtype=torch.int32, device=dev).view(-1, 4)
+        start = torch.clamp(torch.arange(N + 1, dtype=torch.int32, device=dev), max=boxed)
+        mask = torch.zeros((N, 1, H, W), dtype=torch.bool, device=dev)
+        for n, (x, y) in enumerate(xy):
+            mask[n, :, y:y + bs, x:x + bs] = True
+        gb = 2 * packed.numel() / 1e9
+        what = {N: f"one {bs}x{bs} box each", 0: "no boxes (no LDS reserved)",
+                1: f"one {bs}x{bs} box in frame 0 only (LDS reserved, every other tile copies)"}[boxed]
+        emit(f"{N} frames of {H}x{W}, {what} ({gb:.3f} GB per launch):")
+
+        def k_copy():
+            out2.copy_(packed)
+
+        for k in (15, 31, 51):
+            w = gaussian_weights(k)
+            r = (k - 1) // 2
+            wt = torch.from_numpy(w).to(dev)
+            wh, wv = wt.view(1, 1, 1, k).repeat(3, 1, 1, 1), wt.view(1, 1, k, 1).repeat(3, 1, 1, 1)
+
+            def k_blur():
+                K.frames_box_blur(packed, desc, boxes, start, w, H, W, out=out)
+
+            def eager(chunk=256):
+                res = []
+                for i in range(0, N, chunk):
+                    x = src[i:i + chunk].permute(0, 3, 1, 2).float()
+                    y = Fn.conv2d(Fn.pad(x, (r, r, 0, 0), mode="reflect"), wh, groups=3)
+                    y = Fn.conv2d(Fn.pad(y, (0, 0, r, r), mode="reflect"), wv, groups=3)
+                    y = torch.where(mask[i:i + chunk], y.round().clamp_(0, 255), x)
+                    res.append(y.to(torch.uint8).permute(0, 2, 3, 1))
+                return torch.cat(res)
+
+            for fn in (k_blur, k_copy):                 # warm-up: code objects, allocator
+                for _ in range(3):
+                    fn()
+            ref = eager()
+            torch.cuda.synchronize()
+            d = (ref.reshape(-1).int() - out.int()).abs()
+            diff, frac = int(d.max()), float((d > 0).float().mean())
+            del ref, d
+            tb, tc, te = [], [], []
+            for _ in range(rounds):                     # alternate the three paths
+                tb += _rounds(k_blur, reps, 1)
+                tc += _rounds(k_copy, reps, 1)
+                te += _rounds(eager, 1, 1)
+            mb, mc, me = statistics.median(tb), statistics.median(tc), statistics.median(te)
+            emit(f"  k={k}: sm_frames_box_blur {_fmt(tb)}  {gb / mb * 1e3:.0f} GB/s; out.copy_(packed) {_fmt(tc)}  "
+                         f"{gb / mc * 1e3:.0f} GB/s; blur / copy time: {mb / mc:.2f}")
+            emit(f"        eager torch ops (float, pad, conv2d x 2, where, round, uint8): {_fmt(te)}  {me / mb:.1f}x "
+                         f"the kernel; max |eager - kernel| = {diff} grey levels, {frac:.2e} of the bytes differ")
+            torch.cuda.empty_cache()
+        stats = torch.empty((N, 4), dtype=torch.int64, device=dev)
+
+        def k_stats():
+            K.box_region_stats(packed, out, desc, boxes, start, H, W, stats=stats)
+
+        k_stats()
+        ts = _rounds(k_stats, reps, rounds)
+        emit(f"  sm_box_region_stats (memset + launch, original against the k=51 result): {_fmt(ts)}; "
+                     f"box pixels per frame {stats[:, 0].float().mean().item():.0f}")
+        del src, packed, out, out2, mask
+        torch.cuda.empty_cache()
+    emit(_copy_calibration(rounds)[0])
+    emit("agreement with OpenCV's 8-bit cv2.GaussianBlur: NOT MEASURED (no OpenCV on this system)")
+    text = "\n".join(lines) + "\n"
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] in ("resize", "crop", "fedround", "finetune", "fed_dp", "fed_q8", "knn"):
+    if len(sys.argv) > 1 and sys.argv[1] in ("resize", "crop", "fedround", "finetune", "fed_dp", "fed_q8", "knn", "blur"):
         out = sys.argv[3] if len(sys.argv) > 3 and sys.argv[2] == "--out" else None
         {"resize": resize, "crop": crop, "fedround": fedround, "finetune": finetune, "fed_dp": fed_dp, "fed_q8": fed_q8,
-         "knn": knn}[sys.argv[1]](out)
+         "knn": knn, "blur": blur}[sys.argv[1]](out)
     else:
         main()
         frames()

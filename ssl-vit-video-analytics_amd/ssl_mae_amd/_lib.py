@@ -159,6 +159,9 @@ _SIGS = {
                                             _c_p, _c_p]),
     "sm_frames_crop_resize_normalize": (_c_i32, [_c_p, _c_p, _c_i64, _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p,
                                                  _c_i32, _c_p, _c_p]),
+    "sm_frames_box_blur": (_c_i32, [_c_p, _c_p, _c_i64, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_i64, _c_p, _c_i32, _c_p,
+                                    _c_p]),
+    "sm_box_region_stats": (_c_i32, [_c_p, _c_p, _c_p, _c_i64, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_i64, _c_p, _c_p]),
     "sm_motion_scores_workspace_bytes": (_c_i64, [_c_i32] * 5),
     "sm_motion_scores": (_c_i32, [_c_p] + [_c_i32] * 5 + [_c_i64] * 5 + [_c_p, _c_p, _c_i64, _c_p]),
     "sm_topk_frames": (_c_i32, [_c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p]),

@@ -1269,6 +1269,89 @@ def frames_crop_resize_normalize(packed, desc, T, out_hw, mean, std, bgr_swap=Tr
     return _frames_resize("sm_frames_crop_resize_normalize", 8, packed, desc, T, out_hw, mean, std, bgr_swap, out)
 
 
+# ------------------------------------------------------------------ visual privacy (csrc/anonymize.hip)
+BOX_TILE_H, BOX_TILE_W = 32, 64      # SM_BOX_TILE_H / SM_BOX_TILE_W
+BOX_MAX_SIDE = 8192
+BOX_MAX_KSIZE = 63
+
+
+def box_launch_max_frames(max_h, max_w):
+    """The most frames one launch takes at these bounds: N x tiles <= 2^31 - 1 blocks."""
+    tiles = -(-int(max_h) // BOX_TILE_H) * -(-int(max_w) // BOX_TILE_W)
+    return (2 ** 31 - 1) // max(tiles, 1)
+
+
+def _box_batch(name, bufs, desc, boxes, box_start, max_h, max_w):
+    _chk(*bufs, desc, boxes, box_start)
+    dev = bufs[0].device
+    for t in bufs:
+        if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous() or t.numel() != bufs[0].numel():
+            raise _lib.KernelError(f"{name}: pixel buffers must be contiguous 1-D uint8 tensors of one length")
+    if desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != 3 or not desc.is_contiguous():
+        raise _lib.KernelError(f"{name}: desc must be a contiguous int64 [N,3] tensor")
+    if boxes.dtype != torch.int32 or boxes.dim() != 2 or boxes.shape[1] != 4 or not boxes.is_contiguous():
+        raise _lib.KernelError(f"{name}: boxes must be a contiguous int32 [num_boxes,4] tensor")
+    N = desc.shape[0]
+    if box_start.dtype != torch.int32 or box_start.dim() != 1 or box_start.numel() != N + 1 \
+            or not box_start.is_contiguous():
+        raise _lib.KernelError(f"{name}: box_start must be a contiguous int32 [{N + 1}] tensor")
+    if any(t.device != dev for t in (*bufs, desc, boxes, box_start)):
+        raise _lib.KernelError(f"{name}: every tensor must be on one device")
+    max_h, max_w = int(max_h), int(max_w)
+    if not (1 <= max_h <= BOX_MAX_SIDE and 1 <= max_w <= BOX_MAX_SIDE):
+        raise _lib.KernelError(f"{name}: max_h and max_w must lie in [1, {BOX_MAX_SIDE}]")
+    if N > box_launch_max_frames(max_h, max_w):
+        raise _lib.KernelError(f"{name}: {N} frames at {max_h}x{max_w} exceed one launch's "
+                               f"{box_launch_max_frames(max_h, max_w)}")
+    return N, max_h, max_w
+
+
+def frames_box_blur(packed, desc, boxes, box_start, weights, max_h, max_w, out=None):
+    """packed uint8 (1-D; frame n = [H_n,W_n,3] RGB at byte desc[n,0]) + desc int64 [N,3] {byte
+    offset, H, W} + boxes int32 [num_boxes,4] {x, y, w, h} + box_start int32 [N+1] -> uint8 of the
+    same layout: the pixels in the union of a frame's clipped boxes get the separable Gaussian
+    `weights` (host floats, odd length in [3, 63]) of the original frame with reflect-101 edges,
+    every other pixel keeps its bytes; one launch (include/sm_api.h).  A frame whose descriptor is
+    out of range is not written (out=None: those bytes are zero)."""
+    import ctypes
+    name = "frames_box_blur"
+    N, max_h, max_w = _box_batch(name, (packed,), desc, boxes, box_start, max_h, max_w)
+    w = [float(x) for x in weights]
+    if not (3 <= len(w) <= BOX_MAX_KSIZE) or len(w) % 2 == 0:
+        raise _lib.KernelError(f"{name}: the kernel size must be odd and in [3, {BOX_MAX_KSIZE}], got {len(w)}")
+    if out is None:
+        out = torch.zeros_like(packed)
+    else:
+        _chk(out)
+        if out.dtype != torch.uint8 or out.shape != packed.shape or not out.is_contiguous() \
+                or out.device != packed.device:
+            raise _lib.KernelError(f"{name}: out must be a contiguous uint8 tensor like packed")
+        if abs(out.data_ptr() - packed.data_ptr()) < packed.numel():
+            raise _lib.KernelError(f"{name}: out must not overlap packed (the blur reads the original frame)")
+    wv = (ctypes.c_float * len(w))(*w)
+    call("sm_frames_box_blur", ptr(packed), ptr(desc), packed.numel(), N, max_h, max_w, ptr(boxes), ptr(box_start),
+         boxes.shape[0], ctypes.cast(wv, ctypes.c_void_p), len(w), ptr(out), stream())
+    return out
+
+
+def box_region_stats(a, b, desc, boxes, box_start, max_h, max_w, stats=None):
+    """Two buffers of frames_box_blur's layout -> int64 [N,4] = {P, SSE, Ea, Eb} per frame over the
+    union U of its clipped boxes: pixels in U, the sum of (a - b)^2 over U and the channels, and the
+    squared right / down neighbour differences of a and of b at the pixels of U; exact integers,
+    one memset and one launch (include/sm_api.h)."""
+    name = "box_region_stats"
+    N, max_h, max_w = _box_batch(name, (a, b), desc, boxes, box_start, max_h, max_w)
+    if stats is None:
+        stats = torch.zeros((N, 4), dtype=torch.int64, device=a.device)
+    else:
+        _chk(stats)
+        if stats.dtype != torch.int64 or tuple(stats.shape) != (N, 4) or not stats.is_contiguous():
+            raise _lib.KernelError(f"{name}: stats must be a contiguous int64 [{N},4] tensor")
+    call("sm_box_region_stats", ptr(a), ptr(b), ptr(desc), a.numel(), N, max_h, max_w, ptr(boxes), ptr(box_start),
+         boxes.shape[0], ptr(stats), stream())
+    return stats
+
+
 # ------------------------------------------------------------------ streaming dynamic inference
 def _clip5(clip):
     _chk(clip)

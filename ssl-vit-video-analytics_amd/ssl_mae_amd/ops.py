@@ -1443,6 +1443,37 @@ def frames_crop_resize_normalize(packed, desc, T, out_hw, mean, std, bgr_swap=Tr
                                                           bool(bgr_swap))
 
 
+@_op("frames_box_blur", "(Tensor packed, Tensor desc, Tensor boxes, Tensor box_start, float[] weights, int max_h, "
+                        "int max_w) -> Tensor")
+def _frames_box_blur(packed, desc, boxes, box_start, weights, max_h, max_w):
+    return _K.frames_box_blur(packed, desc, boxes, box_start, weights, max_h, max_w)
+
+
+@_frames_box_blur.register_fake
+def _(packed, desc, boxes, box_start, weights, max_h, max_w):
+    return torch.empty_like(packed)
+
+
+def frames_box_blur(packed, desc, boxes, box_start, weights, max_h, max_w):
+    return torch.ops.ssl_mae.frames_box_blur(packed, desc, boxes, box_start, [float(x) for x in weights], int(max_h),
+                                             int(max_w))
+
+
+@_op("box_region_stats", "(Tensor a, Tensor b, Tensor desc, Tensor boxes, Tensor box_start, int max_h, int max_w) "
+                         "-> Tensor")
+def _box_region_stats(a, b, desc, boxes, box_start, max_h, max_w):
+    return _K.box_region_stats(a, b, desc, boxes, box_start, max_h, max_w)
+
+
+@_box_region_stats.register_fake
+def _(a, b, desc, boxes, box_start, max_h, max_w):
+    return a.new_empty((desc.shape[0], 4), dtype=torch.int64)
+
+
+def box_region_stats(a, b, desc, boxes, box_start, max_h, max_w):
+    return torch.ops.ssl_mae.box_region_stats(a, b, desc, boxes, box_start, int(max_h), int(max_w))
+
+
 # ============================================================================ streaming dynamic inference
 @_op("motion_scores", "(Tensor clip) -> Tensor")
 def _motion_scores(clip):
