@@ -463,6 +463,23 @@ int sm_privacy_perturb(const float* z, int64_t N, int D, int G, const float* sig
 int64_t sm_logits_metrics_workspace_bytes(int64_t rows);
 int sm_logits_metrics(const float* logits, int64_t rows, int C, const int64_t* labels, int64_t N, int k,
                       float* dlogits, float grad_scale, double* out, void* ws, int64_t ws_bytes, hipStream_t st);
+/* Cross-entropy of logits [N][C] against a two-label, smoothed target (Mixup / CutMix and label
+ * smoothing in fine-tuning; the reference has neither), sm_logits_metrics' row kernel with another
+ * target: t_c = lam_i s(ya_i)_c + (1 - lam_i) s(yb_i)_c, s(y)_c = eps / C + (1 - eps) [c == y], ya =
+ * labels_a, yb = labels_b (int64 [N]), lam fp32 [N]; a null labels_b or a null lam means lam_i = 1.
+ * loss_i = -sum_c t_c (l_c - logsumexp(l)), formed as (logsumexp(l) - l_ya) - sum_c d_c (l_c - max l)
+ * with d = t - onehot(ya) (sum_c d_c = 0): finite for large logits, and exactly sm_logits_metrics'
+ * loss when the target is the one-hot of ya.  dlogits (nullable) [N][C] <- (softmax(l) - t) *
+ * grad_scale.  out fp64 [2] = sum of the row losses, number of rows whose arg-max is ya_i (ties to
+ * the lower index: the rank rule above with k = 1), the row values added in fp64 in
+ * sm_logits_metrics' order.  With eps == 0 and no labels_b / lam, out[0], out[1] and dlogits equal
+ * those of sm_logits_metrics(..., k = 1, ...) bit for bit.  A label outside [0, C), or a NaN or +inf
+ * logit, makes the row's loss NaN and the row a miss.  -2: C > SM_LOGITS_MAX_CLASSES, eps outside
+ * [0, 1), N < 1 or a null pointer; workspace sm_soft_ce_workspace_bytes(N), 16-byte aligned (else -4). */
+int64_t sm_soft_ce_workspace_bytes(int64_t N);
+int sm_soft_ce(const float* logits, int64_t N, int C, const int64_t* labels_a, const int64_t* labels_b,
+               const float* lam, float eps, float* dlogits, float grad_scale, double* out, void* ws, int64_t ws_bytes,
+               hipStream_t st);
 /* The attacker's hidden layer (src/privacy/attacker.py:11-15 nn.ReLU between two Linears):
  * h[i] = max(pre[i], 0) (NaN stays NaN); backward dpre = dh * (h > 0) and db[c] = sum over the M
  * rows of dpre[.][c] (the first Linear's bias gradient) in the same pass: fp32 partial sums over
@@ -792,6 +809,30 @@ int sm_frames_resize_normalize(const uint8_t* packed, const int64_t* desc, int64
 int sm_frames_crop_resize_normalize(const uint8_t* packed, const int64_t* desc, int64_t packed_bytes, int B, int T,
                                     int Ho, int Wo, const float* mean3, const float* std3, int bgr_swap, float* out,
                                     hipStream_t st);
+
+/* ---- mixing regularisation for fine-tuning (csrc/mix.hip): Mixup and CutMix of a batch with its own
+ * flip in ONE pass (the reference has no augmentation; the pairing is the usual batch-flip rule).
+ * x, out fp32 [B][planes][H][W] contiguous (planes = 3 * T; only the product is used).  Clip b is paired
+ * with clip B - 1 - b: P = B / 2 pairs, lam_px device fp32 [P], box device int32 [P][4] = (y0, x0, h, w),
+ * shared by both clips of a pair.  Per element, a the clip's own pixel and q the partner's pixel at
+ * the same position:
+ *   inside the box, rows [y0, y0 + h) x columns [x0, x0 + w) of EVERY plane (so of every frame: the
+ *   mix is clip-consistent)                     out = q
+ *   outside the box and lam_px == 1             out = a   (a select: a non-finite q does not leak
+ *                                                          through a 0 * q)
+ *   outside the box otherwise                   out = fl(fl(lam_px a) + fl(fl(1 - lam_px) q))
+ * every operation rounded on its own (no fma), so clip b gets lam x[b] + (1 - lam) x[B-1-b] and its
+ * partner lam x[B-1-b] + (1 - lam) x[b]; bit for bit tests/mix_mirror.py.  The middle clip of an odd
+ * batch is copied unchanged.  One thread owns the same element of both clips of a pair, reads each
+ * source element once and writes each output element once, so out == x (in place) is legal; any
+ * other overlap of x and out is not.  16-byte accesses when W % 4 == 0 and x and out are 16-byte
+ * aligned, scalar ones otherwise (same bits).  The box is only a predicate on (row, column), never
+ * an address; a box that leaves the frame or has a negative side must be refused on the host
+ * BEFORE the upload (kernels.clip_mix does), since the table lives on the device.  B == 0: 0.
+ * -2: a null pointer, planes / H / W < 1, B < 0, planes * H * W >= 2^31 or more than 65535 pairs
+ * (the launch's grid limits). */
+int sm_clip_mix(const float* x, int64_t B, int64_t planes, int H, int W, const float* lam_px, const int32_t* box,
+                float* out, hipStream_t st);
 
 /* ---- visual privacy (csrc/anonymize.hip; the anonymisation half of the reference's
  * src/run_privacy.py:118-226 run_visual_privacy: cv2.GaussianBlur over detected boxes.  The detector

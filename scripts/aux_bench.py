@@ -41,6 +41,11 @@
   51 on 2048 frames with and without boxes, against a plain device copy of the same bytes and the
   same result in eager torch ops, the statistics launch, and the 4.9 GB copy calibration (see `blur`).
 
+* `aux_bench.py mix [--out profiles/mix.txt]`: the Mixup / CutMix launch (sm_clip_mix) at 256 clips x 8
+  frames, 112^2 and 224^2, all-Mixup and all-CutMix pairs, against a plain device copy of the same
+  tensor and the same result in eager torch ops, the device operations ClipMixer adds to a step, and
+  the 4.9 GB copy calibration (see `mix`).
+
 Prints one JSON line per kernel; run under rocprofv3 --kernel-trace --stats to
 cross-check the average launch durations."""
 import json
@@ -912,11 +917,96 @@ def blur(out_path=None, N=2048, reps=10, rounds=5):
             f.write(text)
 
 
+def mix(out_path=None, B=256, T=8, reps=10, rounds=5, seed=0):
+    """sm_clip_mix on a [B,3,T,S,S] fp32 batch at S = 112 and 224, with mae_loader.ClipMixer's draws at
+    a fixed seed for all-Mixup pairs (cutmix_alpha 0) and all-CutMix pairs (mixup_alpha 0), out of
+    place; alternating in every round with out.copy_(x) of the same tensor (the kernel moves the same
+    bytes: every element read once and written once) and with the same result from eager torch ops
+    on the device (x * lam + x.flip(0) * (1 - lam), then torch.where on the pairs' box mask).  GB =
+    bytes read + written = 2 x the tensor.  Then the device operations one ClipMixer call adds to a
+    training step, from torch.profiler's trace, and the 4.9 GB copy calibration.  No target is
+    asserted: what is measured is written down."""
+    import statistics
+    from ssl_mae_amd.mae_loader import ClipMixer
+    dev = torch.device("cuda")
+    lines = []
+
+    def emit(line):
+        lines.append(line)
+        print(line, flush=True)
+
+    emit(f"device: {torch.cuda.get_device_name(0)}; B={B} T={T}; draws: ClipMixer(seed={seed}); {rounds} rounds of "
+         f"{reps} launches, alternating, median [min .. max]; GB = bytes read + written = 2 x the tensor")
+    g = torch.Generator(device="cuda").manual_seed(0)
+    P = B // 2
+    for S in (112, 224):
+        x = torch.randn((B, 3, T, S, S), device=dev, generator=g)
+        out, out2 = torch.empty_like(x), torch.empty_like(x)
+        gb = 2 * x.numel() * 4 / 1e9
+        emit(f"[{B},3,{T},{S},{S}] fp32 ({gb:.3f} GB per launch):")
+
+        def k_copy():
+            out2.copy_(x)
+
+        for what, kw in (("all Mixup", {"cutmix_alpha": 0.0}), ("all CutMix", {"mixup_alpha": 0.0})):
+            lam_px, box, weight = ClipMixer(seed=seed, **kw).draw(B, S, S)
+            lam_d, box_d = lam_px.to(dev), box.to(dev)
+            lam_b = torch.cat([lam_px, lam_px.flip(0)]).to(dev).view(B, 1, 1, 1, 1)
+            mask = torch.zeros((B, 1, 1, S, S), dtype=torch.bool, device=dev)
+            for p, (y0, x0, h, w) in enumerate(box.tolist()):
+                mask[p, ..., y0:y0 + h, x0:x0 + w] = True
+                mask[B - 1 - p, ..., y0:y0 + h, x0:x0 + w] = True
+
+            def k_mix():
+                K.clip_mix(x, lam_d, box_d, out=out)
+
+            def eager():
+                xf = x.flip(0)
+                return torch.where(mask, xf, x * lam_b + xf * (1 - lam_b))
+
+            for fn in (k_mix, k_copy, eager):             # warm-up: code objects, allocator
+                for _ in range(3):
+                    fn()
+            torch.cuda.synchronize()
+            diff = float((eager() - out).abs().max())
+            tm, tc, te = [], [], []
+            for _ in range(rounds):                       # alternate the three paths
+                tm += _rounds(k_mix, reps, 1)
+                tc += _rounds(k_copy, reps, 1)
+                te += _rounds(eager, 2, 1)
+            mm, mc, me = statistics.median(tm), statistics.median(tc), statistics.median(te)
+            area = sum(h * w for _, _, h, w in box.tolist()) / max(P, 1) / (S * S)
+            emit(f"  {what} (mean label weight {float(weight.mean()):.3f}, mean box {area:.3f} of the frame): sm_clip_mix "
+                 f"{_fmt(tm)}  {gb / mm * 1e3:.0f} GB/s; out.copy_(x) {_fmt(tc)}  {gb / mc * 1e3:.0f} GB/s; "
+                 f"mix / copy time: {mm / mc:.3f}")
+            emit(f"      eager torch ops (flip, two products, sum, where): {_fmt(te)}  {me / mm:.1f}x the kernel; "
+                 f"max |eager - kernel| = {diff:.2e}")
+            torch.cuda.empty_cache()
+        del x, out, out2
+        torch.cuda.empty_cache()
+    clip = torch.randn((8, 3, T, 112, 112), device=dev, generator=g)
+    label = torch.arange(8, device=dev)
+    mixer = ClipMixer(seed=seed)
+    try:
+        emit(f"device operations one ClipMixer call adds to a step (torch.profiler's trace: kernels, memsets, copies): "
+             f"{_count_launches(lambda: mixer(clip, label))} = the table's upload, sm_clip_mix, and label.flip(0) for the "
+             "partner labels")
+    except Exception as exc:  # the trace is a cross-check, not the measurement
+        emit(f"device operations one ClipMixer call adds to a step: not measured ({type(exc).__name__}); by construction "
+             "the table's upload, sm_clip_mix, and label.flip(0) for the partner labels")
+    emit(_copy_calibration(rounds)[0])
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] in ("resize", "crop", "fedround", "finetune", "fed_dp", "fed_q8", "knn", "blur"):
+    if len(sys.argv) > 1 and sys.argv[1] in ("resize", "crop", "fedround", "finetune", "fed_dp", "fed_q8", "knn", "blur",
+                                             "mix"):
         out = sys.argv[3] if len(sys.argv) > 3 and sys.argv[2] == "--out" else None
         {"resize": resize, "crop": crop, "fedround": fedround, "finetune": finetune, "fed_dp": fed_dp, "fed_q8": fed_q8,
-         "knn": knn, "blur": blur}[sys.argv[1]](out)
+         "knn": knn, "blur": blur, "mix": mix}[sys.argv[1]](out)
     else:
         main()
         frames()

@@ -5,6 +5,8 @@
 //   privacy_perturb   out[g] = (z + sigma_g n_g(r, c)) keep_g(r, c) for G configurations, z read once
 //   logits_metrics    per row cross-entropy / entropy / top-1 / top-k (+ the softmax gradient),
 //                     summed per segment in fp64
+//   soft_ce           the same row kernel against a two-label, smoothed target (Mixup / CutMix and
+//                     label smoothing in fine-tuning): loss, top-1 and the gradient
 //   relu_fwd          h = max(pre, 0)
 //   relu_bias_bwd     dpre = dh (h > 0) and its column sums in one pass
 // No atomics, no LDS tiling, no MFMA; every reduction has a fixed partition and order, so no
@@ -89,13 +91,40 @@ SM_DEV float pad_neg_inf(float x, int in) {
   return __int_as_float((__float_as_int(x) & in) | ((int)0xFF800000 & ~in));
 }
 
+// The row kernel's target.  HardTarget: the one-hot of labels[r % N] (sm_logits_metrics).
+// SoftTarget (sm_soft_ce): t_c = lam s(ya)_c + (1 - lam) s(yb)_c with s(y)_c = eps / C + (1 - eps) [c == y],
+// ya = labels[r], yb = labels_b[r] (null: ya), lam = lam[r] (null: 1).
+struct HardTarget {
+  static constexpr bool soft = false;
+};
+struct SoftTarget {
+  static constexpr bool soft = true;
+  const int64_t* labels_b;
+  const float* lam;
+  float eps;
+};
+// One row's soft target.  With eps == 0 and lam == 1 it is exactly 1 at ya and exactly 0 elsewhere.
+struct SoftRow {
+  int ya, yb;
+  float lam, oml, off, on;                            // oml = 1 - lam, off = eps / C, on = 1 - eps
+  SM_DEV float t(int c) const {
+    const float ta = off + (c == ya ? on : 0.f), tb = off + (c == yb ? on : 0.f);
+    return lam * ta + oml * tb;
+  }
+};
+
 // One wave per row, four rows per block.  Lane l owns columns 256 j + 4 l + i (j < NG, i < 4):
 // NG 16-byte groups in registers.  rowvals [rows][4] = loss, entropy, hit1, hitk.
-template <int NG, bool VEC>
+// Target::soft: rowvals [rows][2] = loss, hit1 (no entropy, k unused), the gradient is softmax - t, and
+// the loss is (lse - l_ya) - sum_c d_c (l_c - m) with d = t - onehot(ya) (sum_c d_c = 0, so this is
+// lse - sum_c t_c l_c): the hard kernel's expression plus a correction formed from the max-subtracted
+// logits, which is finite for large logits and exactly 0 when the target is the one-hot of ya.
+template <int NG, bool VEC, typename Target>
 __global__ __launch_bounds__(kThreads) void logits_rows_kernel(const float* __restrict__ logits, int64_t rows, int C,
                                                                const int64_t* __restrict__ labels, int64_t N, int k,
                                                                float* __restrict__ dlogits, float grad_scale,
-                                                               float* __restrict__ rowvals) {
+                                                               float* __restrict__ rowvals, Target tgt) {
+  constexpr bool SOFT = Target::soft;
   const int lane = threadIdx.x & 63;
   const int64_t r = blockIdx.x * (int64_t)(kThreads / 64) + (threadIdx.x >> 6);
   if (r >= rows) return;                              // wave-uniform
@@ -126,7 +155,19 @@ __global__ __launch_bounds__(kThreads) void logits_rows_kernel(const float* __re
   const bool y_ok = y64 >= 0 && y64 < C;
   const int y = y_ok ? (int)y64 : -1;
   const float lx = x[y_ok ? y : 0];                    // the label's logit: one wave-uniform load
-  const float ly = y_ok ? lx : NAN;
+  bool t_ok = y_ok;                                    // every label of the target lies in [0, C)
+  SoftRow sr;
+  if constexpr (SOFT) {
+    const int64_t yb64 = tgt.labels_b ? tgt.labels_b[r] : y64;
+    t_ok = y_ok && yb64 >= 0 && yb64 < C;
+    sr.ya = y;
+    sr.yb = t_ok ? (int)yb64 : -1;
+    sr.lam = tgt.labels_b && tgt.lam ? tgt.lam[r] : 1.0f;
+    sr.oml = 1.0f - sr.lam;
+    sr.off = tgt.eps / (float)C;
+    sr.on = 1.0f - tgt.eps;
+  }
+  const float ly = t_ok ? lx : NAN;
   float m = -INFINITY;
 #pragma unroll
   for (int j = 0; j < NG; ++j)
@@ -134,6 +175,7 @@ __global__ __launch_bounds__(kThreads) void logits_rows_kernel(const float* __re
     for (int i = 0; i < 4; ++i) m = fmaxf(m, v[j][i]);
   m = wave_max(m);
   float s = 0.f;
+  float corr = 0.f;                                    // SOFT: sum_c d_c (l_c - m)
   int rank = 0;
 #pragma unroll
   for (int j = 0; j < NG; ++j)
@@ -147,8 +189,15 @@ __global__ __launch_bounds__(kThreads) void logits_rows_kernel(const float* __re
       const float e = expf(l - m);                       // a NaN or +inf logit makes the sum NaN
       s += e;
       v[j][i] = e;
+      if constexpr (SOFT) {
+        // a column whose weight does not move (d == 0) adds nothing, whatever its logit (-inf is an
+        // ordinary value); padding slots (c >= C) have no target
+        const float d = sr.t(c) - (c == y ? 1.0f : 0.0f);
+        corr += c < C && d != 0.f ? d * (l - m) : 0.f;
+      }
     }
   s = wave_sum(s);
+  if constexpr (SOFT) corr = wave_sum(corr);
   rank = wave_sum_i(rank);
   const float lse = m + logf(s);
   const float inv = 1.0f / s;
@@ -157,11 +206,14 @@ __global__ __launch_bounds__(kThreads) void logits_rows_kernel(const float* __re
   for (int j = 0; j < NG; ++j)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const float p = v[j][i] * inv;
-      ent -= p * logf(p + 1e-12f);                      // metrics_privacy.py:7; padding: p = 0 adds 0
+      float p = v[j][i] * inv;
+      // SOFT has no entropy to keep p a value of its own: without this (empty) statement the compiler
+      // contracts e * inv - t into one fma and the gradient loses the hard form's rounding of p
+      if constexpr (SOFT) asm volatile("" : "+v"(p));
+      if constexpr (!SOFT) ent -= p * logf(p + 1e-12f);   // metrics_privacy.py:7; padding: p = 0 adds 0
       v[j][i] = p;
     }
-  ent = wave_sum(ent);
+  if constexpr (!SOFT) ent = wave_sum(ent);
   if (dlogits) {
     float* d = dlogits + r * C;
 #pragma unroll
@@ -169,7 +221,10 @@ __global__ __launch_bounds__(kThreads) void logits_rows_kernel(const float* __re
       const int c0 = 256 * j + 4 * lane;
       float gq[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) gq[i] = (v[j][i] - (c0 + i == y ? 1.0f : 0.0f)) * grad_scale;
+      for (int i = 0; i < 4; ++i) {
+        if constexpr (SOFT) gq[i] = (v[j][i] - sr.t(c0 + i)) * grad_scale;
+        else gq[i] = (v[j][i] - (c0 + i == y ? 1.0f : 0.0f)) * grad_scale;
+      }
       if constexpr (VEC) {
         if (c0 < C) *(f32x4*)(d + c0) = f32x4{gq[0], gq[1], gq[2], gq[3]};
       } else if (256 * j + 256 <= C) {                  // wave-uniform: a whole 256-column slab
@@ -185,12 +240,28 @@ __global__ __launch_bounds__(kThreads) void logits_rows_kernel(const float* __re
   if (lane == 0) {
     const float loss = lse - ly;
     const bool finite = fabsf(lse) < INFINITY && y_ok && ly == ly;   // false for NaN
-    float* o = rowvals + r * 4;
-    o[0] = loss;
-    o[1] = ent;
-    o[2] = finite && rank < 1 ? 1.f : 0.f;
-    o[3] = finite && rank < k ? 1.f : 0.f;
+    if constexpr (SOFT) {
+      float* o = rowvals + r * 2;
+      o[0] = loss - corr;
+      o[1] = finite && rank < 1 ? 1.f : 0.f;
+    } else {
+      float* o = rowvals + r * 4;
+      o[0] = loss;
+      o[1] = ent;
+      o[2] = finite && rank < 1 ? 1.f : 0.f;
+      o[3] = finite && rank < k ? 1.f : 0.f;
+    }
   }
+}
+
+// The row kernel of the class-count tier of C
+template <bool VEC, typename Target>
+auto rows_kernel_for(int C) {
+  return C <= 256    ? logits_rows_kernel<1, VEC, Target>
+         : C <= 512  ? logits_rows_kernel<2, VEC, Target>
+         : C <= 1024 ? logits_rows_kernel<4, VEC, Target>
+         : C <= 2048 ? logits_rows_kernel<8, VEC, Target>
+                     : logits_rows_kernel<16, VEC, Target>;
 }
 
 // out[s][q] = sum over the N rows of segment s of rowvals[.][q], fp64: thread t takes rows t,
@@ -208,6 +279,20 @@ __global__ __launch_bounds__(kThreads) void logits_segments_kernel(const float* 
   static_assert(kThreads == 256, "thread_order_sum_d adds 256 threads' partials");
   thread_order_sum_d<4, SUM_FIRST_K>(a);               // thread q < 4: column q's sum in a[0]
   if (tid < 4) out[(int64_t)s * 4 + tid] = a[0];
+}
+
+// out[q] = sum over the N rows of rowvals[.][q] (q < 2), in logits_segments_kernel's order: the loss
+// sum of a one-hot target has sm_logits_metrics' bits
+__global__ __launch_bounds__(kThreads) void soft_sum_kernel(const float* __restrict__ rowvals, int64_t N,
+                                                            double* __restrict__ out) {
+  const int tid = threadIdx.x;
+  double a[2] = {0.0, 0.0};
+  for (int64_t i = tid; i < N; i += kThreads) {
+    a[0] += (double)rowvals[i * 2];
+    a[1] += (double)rowvals[i * 2 + 1];
+  }
+  thread_order_sum_d<2, SUM_FIRST_K>(a);               // thread q < 2: column q's sum in a[0]
+  if (tid < 2) out[tid] = a[0];
 }
 
 // ---------------------------------------------------------------- ReLU
@@ -303,17 +388,33 @@ extern "C" int sm_logits_metrics(const float* logits, int64_t rows, int C, const
   if (!ws || ws_bytes < sm_logits_metrics_workspace_bytes(rows) || !aligned16(ws)) return -4;
   float* rowvals = (float*)ws;
   const bool vec = C % 4 == 0 && aligned16(logits) && (!dlogits || aligned16(dlogits));
-  DISPATCH_BOOL(vec, VEC, {
-    const auto rows_kernel = C <= 256    ? logits_rows_kernel<1, VEC>
-                             : C <= 512  ? logits_rows_kernel<2, VEC>
-                             : C <= 1024 ? logits_rows_kernel<4, VEC>
-                             : C <= 2048 ? logits_rows_kernel<8, VEC>
-                                         : logits_rows_kernel<16, VEC>;
-    hipLaunchKernelGGL(rows_kernel, dim3((unsigned)nblk), dim3(kThreads), 0, st, logits, rows, C, labels, N, k, dlogits,
-                       grad_scale, rowvals);
-  });
+  DISPATCH_BOOL(vec, VEC,
+                hipLaunchKernelGGL((rows_kernel_for<VEC, HardTarget>(C)), dim3((unsigned)nblk), dim3(kThreads), 0, st,
+                                   logits, rows, C, labels, N, k, dlogits, grad_scale, rowvals, HardTarget{}));
   SM_CHECK_LAUNCH();
   hipLaunchKernelGGL(logits_segments_kernel, dim3((unsigned)S), dim3(kThreads), 0, st, rowvals, N, out);
+  SM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int64_t sm_soft_ce_workspace_bytes(int64_t N) { return N > 0 ? N * 2 * (int64_t)sizeof(float) : 0; }
+
+extern "C" int sm_soft_ce(const float* logits, int64_t N, int C, const int64_t* labels_a, const int64_t* labels_b,
+                          const float* lam, float eps, float* dlogits, float grad_scale, double* out, void* ws,
+                          int64_t ws_bytes, hipStream_t st) {
+  if (N <= 0 || C <= 0 || C > SM_LOGITS_MAX_CLASSES || !(eps >= 0.f && eps < 1.f) || !logits || !labels_a || !out)
+    return -2;
+  const int64_t nblk = (N + kThreads / 64 - 1) / (kThreads / 64);
+  if (nblk > 0x7fffffff) return -2;
+  if (!ws || ws_bytes < sm_soft_ce_workspace_bytes(N) || !aligned16(ws)) return -4;
+  float* rowvals = (float*)ws;
+  const bool vec = C % 4 == 0 && aligned16(logits) && (!dlogits || aligned16(dlogits));
+  DISPATCH_BOOL(vec, VEC,
+                hipLaunchKernelGGL((rows_kernel_for<VEC, SoftTarget>(C)), dim3((unsigned)nblk), dim3(kThreads), 0, st,
+                                   logits, N, C, labels_a, N, 1, dlogits, grad_scale, rowvals,
+                                   SoftTarget{labels_b, lam, eps}));
+  SM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(soft_sum_kernel, dim3(1), dim3(kThreads), 0, st, rowvals, N, out);
   SM_CHECK_LAUNCH();
   return 0;
 }

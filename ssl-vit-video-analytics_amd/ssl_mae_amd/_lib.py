@@ -162,6 +162,7 @@ _SIGS = {
     "sm_frames_box_blur": (_c_i32, [_c_p, _c_p, _c_i64, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_i64, _c_p, _c_i32, _c_p,
                                     _c_p]),
     "sm_box_region_stats": (_c_i32, [_c_p, _c_p, _c_p, _c_i64, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_i64, _c_p, _c_p]),
+    "sm_clip_mix": (_c_i32, [_c_p, _c_i64, _c_i64, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p]),
     "sm_motion_scores_workspace_bytes": (_c_i64, [_c_i32] * 5),
     "sm_motion_scores": (_c_i32, [_c_p] + [_c_i32] * 5 + [_c_i64] * 5 + [_c_p, _c_p, _c_i64, _c_p]),
     "sm_topk_frames": (_c_i32, [_c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p]),
@@ -174,6 +175,8 @@ _SIGS = {
     "sm_logits_metrics_workspace_bytes": (_c_i64, [_c_i64]),
     "sm_logits_metrics": (_c_i32, [_c_p, _c_i64, _c_i32, _c_p, _c_i64, _c_i32, _c_p, _c_f32, _c_p, _c_p, _c_i64,
                                    _c_p]),
+    "sm_soft_ce_workspace_bytes": (_c_i64, [_c_i64]),
+    "sm_soft_ce": (_c_i32, [_c_p, _c_i64, _c_i32, _c_p, _c_p, _c_p, _c_f32, _c_p, _c_f32, _c_p, _c_p, _c_i64, _c_p]),
     "sm_relu_fwd": (_c_i32, [_c_p, _c_i64, _c_p, _c_p]),
     "sm_relu_bias_bwd_workspace_bytes": (_c_i64, [_c_i64, _c_i32]),
     "sm_relu_bias_bwd": (_c_i32, [_c_p, _c_p, _c_i64, _c_i32, _c_p, _c_p, _c_p, _c_i64, _c_p]),

@@ -28,9 +28,11 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", CSRC, "-I
 # plain segments repeat fed.hip's arithmetic: the noise's explicit fma is its only one.
 # fed_q8.hip's quantisation is matched operation by operation by a host mirror as well: no fma at all.
 # anonymize.hip's Gaussian taps are separately rounded products and sums, matched by a host mirror: no fma.
+# mix.hip's blend lam a + (1 - lam) q is two separately rounded products and their sum, matched by a host mirror: no fma.
 FILE_FLAGS = {"fed.hip": ["-ffp-contract=off"], "temporal.hip": ["-ffp-contract=off"],
               "resize.hip": ["-ffp-contract=off"], "fed_dp.hip": ["-ffp-contract=off"],
               "fed_q8.hip": ["-ffp-contract=off"], "anonymize.hip": ["-ffp-contract=off"],
+              "mix.hip": ["-ffp-contract=off"],
               "attention.hip": ["-fno-slp-vectorize"], "gemm.hip": ["-fno-slp-vectorize"]}
 
 

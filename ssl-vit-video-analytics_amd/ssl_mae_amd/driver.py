@@ -7,7 +7,7 @@ in utils, TopCEFn and load_finetune_ckpt in finetune).
 import torch
 
 from . import ops as K    # every kernel launch through the torch.ops.ssl_mae dispatcher
-from .finetune import TopCEFn, VideoClassifier, load_finetune_ckpt
+from .finetune import SoftCEFn, TopCEFn, VideoClassifier, load_finetune_ckpt
 from .utils import set_seed
 
 
@@ -173,20 +173,37 @@ def split_file_loader(split, *, clip_len, stride, image_size, batch_size, num_wo
 
 
 # ------------------------------------------------------------------ supervised pass / evaluation
-def train_pass(model, loader, opt, device, amp, sums, scaler=None, on_step=None):
+def train_pass(model, loader, opt, device, amp, sums, scaler=None, on_step=None, *, mixer=None, label_smoothing=0.0,
+               on_mix=None):
     """One supervised pass over `loader`: bf16 autocast when `amp`, the cross-entropy through
     sm_logits_metrics (TopCEFn), backward and the optimizer step (through `scaler` when given).
     Adds (loss, loss * batch) of every step to the float64 device pair `sums`, so the caller
     reads back once, whenever it wants; returns (steps, samples).  `on_step(step, loss, logits,
-    label)` runs after every optimizer step with detached device tensors."""
+    label)` runs after every optimizer step with detached device tensors.
+
+    `mixer` (a mae_loader.ClipMixer) mixes every batch with its own flip before the forward pass
+    and `label_smoothing` in (0, 1) smooths the target; with either the loss is the soft
+    cross-entropy of sm_soft_ce (SoftCEFn) against the mixed, smoothed target, and `loss` is that
+    value.  `on_step` still gets the batch's own labels; `on_mix(step, labels_b, lam)` runs right
+    after the mix with the partner labels and the labels' weights (device tensors).  With both at
+    their defaults the step is the one above, untouched."""
+    soft = mixer is not None or float(label_smoothing) != 0.0
     steps = samples = 0
     for step, (clip, label) in enumerate(loader):
         clip = clip.to(device, non_blocking=True)
         label = label.to(device, non_blocking=True).long()
         opt.zero_grad(set_to_none=True)
+        labels_b = lam = None
+        if mixer is not None:
+            clip, _, labels_b, lam = mixer(clip, label)
+            if on_mix is not None:
+                on_mix(step, labels_b, lam)
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bool(amp)):
             logits = model(clip)
-        loss = TopCEFn.apply(logits, label)
+        if soft:
+            loss = SoftCEFn.apply(logits, label, labels_b, lam, float(label_smoothing))
+        else:
+            loss = TopCEFn.apply(logits, label)
         if scaler is not None:
             scaler.scale(loss).backward()
             scaler.step(opt)

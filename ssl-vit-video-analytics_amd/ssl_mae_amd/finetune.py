@@ -91,6 +91,25 @@ class TopCEFn(torch.autograd.Function):
         return ctx.saved_tensors[0] * g, None
 
 
+class SoftCEFn(torch.autograd.Function):
+    """The mean cross-entropy against the mixed, smoothed target lam s(labels_a) + (1 - lam)
+    s(labels_b), s(y) = eps / C + (1 - eps) onehot(y), through sm_soft_ce (labels_b = lam = None: the
+    smoothed labels_a alone); its dlogits output is the gradient.  TopCEFn with another target."""
+
+    @staticmethod
+    def forward(ctx, logits, labels_a, labels_b, lam, eps):
+        logits = logits.float().contiguous()
+        n = logits.shape[0]
+        dl = torch.empty_like(logits)
+        m = K.soft_ce(logits, labels_a, labels_b, lam, eps, dl, 1.0 / n)
+        ctx.save_for_backward(dl)
+        return (m[0] / n).float()
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.saved_tensors[0] * g, None, None, None, None
+
+
 class TinyViTBackbone(TinyViT):
     """TinyViT (tiny_vit_21m_variant) with the backbone contract of
     MobileViTBackbone.forward (mobilevit.py:157-166): x [N,3,H,W] -> (feat [N,576,h,w],

@@ -1269,6 +1269,57 @@ def frames_crop_resize_normalize(packed, desc, T, out_hw, mean, std, bgr_swap=Tr
     return _frames_resize("sm_frames_crop_resize_normalize", 8, packed, desc, T, out_hw, mean, std, bgr_swap, out)
 
 
+# ------------------------------------------------------------------ Mixup / CutMix (csrc/mix.hip)
+MIX_MAX_PAIRS = 65535     # one grid row per pair
+
+
+def mix_boxes_check(boxes, H, W):
+    """Host rows (y0, x0, h, w): every box must lie inside the H x W frame and have no negative
+    side (an empty box, h == 0 or w == 0, is fine anywhere inside)."""
+    for p, (y0, x0, h, w) in enumerate(boxes):
+        if y0 < 0 or x0 < 0 or h < 0 or w < 0 or y0 + h > H or x0 + w > W:
+            raise _lib.KernelError(f"clip_mix: pair {p}: box rows [{y0}, {y0 + h}) x columns [{x0}, {x0 + w}) has a "
+                                   f"negative side or leaves the {H}x{W} frame")
+
+
+def clip_mix(x, lam_px, box, out=None):
+    """x fp32 [B, ..., H, W] (contiguous; a [B,3,T,H,W] clip batch) -> the batch mixed with its own
+    flip, clip b with clip B-1-b, in one launch (sm_clip_mix, include/sm_api.h): inside pair p's box
+    (y0, x0, h, w), on every plane, the partner's pixel; outside it the clip's own pixel when
+    lam_px[p] == 1 and lam_px[p] * own + (1 - lam_px[p]) * partner otherwise.  lam_px fp32 [B//2],
+    box int32 [B//2, 4].  Given as HOST tensors they are checked here (mix_boxes_check) and go up
+    in one copy; given on the device they are used as they are, and the boxes are the CALLER's
+    guarantee (they are not read back; mae_loader.ClipMixer checks its table before the upload).
+    out=None allocates; out may be x itself (in place), no other overlap."""
+    _chk(x, out)
+    if x.dim() < 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise _lib.KernelError("clip_mix takes a contiguous fp32 [B, ..., H, W] tensor")
+    B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    P = B // 2
+    planes = x[0].numel() // max(H * W, 1) if B else 0
+    if B and (H < 1 or W < 1 or planes < 1 or planes * H * W >= 2 ** 31 or P + B % 2 > MIX_MAX_PAIRS):
+        raise _lib.KernelError(f"clip_mix: a clip needs 1 <= elements < 2^31 and the batch at most {MIX_MAX_PAIRS} pairs")
+    if lam_px.dtype != torch.float32 or tuple(lam_px.shape) != (P,) or not lam_px.is_contiguous():
+        raise _lib.KernelError(f"clip_mix: lam_px must be contiguous fp32 [{P}]")
+    if box.dtype != torch.int32 or tuple(box.shape) != (P, 4) or not box.is_contiguous():
+        raise _lib.KernelError(f"clip_mix: box must be contiguous int32 [{P},4]")
+    if lam_px.device != box.device or (lam_px.is_cuda and lam_px.device != x.device):
+        raise _lib.KernelError("clip_mix: lam_px and box must both be host tensors or both be on x's device")
+    if not lam_px.is_cuda:
+        mix_boxes_check(box.tolist(), H, W)
+        table = torch.cat([box.reshape(-1), lam_px.view(torch.int32)]).to(x.device)     # one copy
+        box, lam_px = table[:4 * P].view(P, 4), table[4 * P:].view(torch.float32)
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.dtype != torch.float32 or out.shape != x.shape or not out.is_contiguous() or out.device != x.device:
+        raise _lib.KernelError("clip_mix: out must be a contiguous fp32 tensor like x")
+    elif out.data_ptr() != x.data_ptr() and abs(out.data_ptr() - x.data_ptr()) < 4 * x.numel():
+        raise _lib.KernelError("clip_mix: out may be x itself, but must not overlap it otherwise")
+    call("sm_clip_mix", ptr(x), B, planes, H, W, ptr(lam_px) if P else None, ptr(box) if P else None, ptr(out),
+         stream())
+    return out
+
+
 # ------------------------------------------------------------------ visual privacy (csrc/anonymize.hip)
 BOX_TILE_H, BOX_TILE_W = 32, 64      # SM_BOX_TILE_H / SM_BOX_TILE_W
 BOX_MAX_SIDE = 8192
@@ -1487,6 +1538,41 @@ def logits_metrics(logits, labels, k, segments=1, dlogits=None, grad_scale=1.0):
     ws = _ws(nbytes, logits.device)
     call("sm_logits_metrics", ptr(logits), rows, C, ptr(labels), N, int(k), ptr(dlogits), float(grad_scale), ptr(out),
          ptr(ws), nbytes, stream())
+    return out
+
+
+def soft_ce(logits, labels_a, labels_b=None, lam=None, eps=0.0, dlogits=None, grad_scale=1.0):
+    """logits fp32 [N, C], labels_a (and labels_b) int64 [N], lam fp32 [N] -> fp64 [2]: the sum of the
+    cross-entropies against t = lam s(labels_a) + (1 - lam) s(labels_b), s(y) = eps / C + (1 - eps)
+    onehot(y), and the rows whose arg-max is labels_a (sm_soft_ce).  labels_b and lam come together
+    or not at all (then t = s(labels_a)).  dlogits (fp32, logits' shape, optional) receives
+    (softmax - t) * grad_scale.  With eps == 0 and no partner the sum, the hits and dlogits have
+    logits_metrics(logits, labels_a, 1)'s bits."""
+    _f32_2d(logits, "soft_ce: logits")
+    _chk(labels_a, labels_b, lam, dlogits)
+    N, C = logits.shape
+    if not 1 <= C <= LOGITS_MAX_CLASSES:
+        raise _lib.KernelError(f"soft_ce: the class count must be in [1, {LOGITS_MAX_CLASSES}], got {C}")
+    if (labels_b is None) != (lam is None):
+        raise _lib.KernelError("soft_ce: give both labels_b and lam (a mixed target) or neither")
+    for t, what in ((labels_a, "labels_a"), (labels_b, "labels_b")):
+        if t is not None and (t.dtype != torch.int64 or tuple(t.shape) != (N,) or not t.is_contiguous()
+                              or t.device != logits.device):
+            raise _lib.KernelError(f"soft_ce: {what} must be a contiguous int64 [{N}] vector on the logits' device")
+    if lam is not None and (lam.dtype != torch.float32 or tuple(lam.shape) != (N,) or not lam.is_contiguous()
+                            or lam.device != logits.device):
+        raise _lib.KernelError(f"soft_ce: lam must be a contiguous fp32 [{N}] vector on the logits' device")
+    eps = float(eps)
+    if not 0.0 <= eps < 1.0:
+        raise _lib.KernelError(f"soft_ce: eps must lie in [0, 1), got {eps}")
+    if dlogits is not None and (dlogits.dtype != torch.float32 or dlogits.shape != logits.shape
+                                or not dlogits.is_contiguous()):
+        raise _lib.KernelError("soft_ce: dlogits must match the logits (contiguous fp32)")
+    out = torch.empty(2, dtype=torch.float64, device=logits.device)
+    nbytes = query("sm_soft_ce_workspace_bytes", N)
+    ws = _ws(nbytes, logits.device)
+    call("sm_soft_ce", ptr(logits), N, C, ptr(labels_a), ptr(labels_b), ptr(lam), eps, ptr(dlogits), float(grad_scale),
+         ptr(out), ptr(ws), nbytes, stream())
     return out
 
 

@@ -309,6 +309,92 @@ class ClipResizer:
         return op(p.contiguous(), d.contiguous(), int(T), self.out_hw, self.mean, self.std, self.bgr_swap)
 
 
+class ClipMixer:
+    """Clip-consistent Mixup / CutMix of a training batch with its own flip (clip b with clip
+    B-1-b, P = B // 2 pairs; the usual batch-flip rule, the reference has no augmentation).  A host
+    sampler like RandomResizedCropFlip: `mixer(clip, label)` draws one decision per pair, uploads
+    ONE small table and launches sm_clip_mix out of place; nothing is read back.
+
+    Per pair, with probability `prob` it is mixed: by CutMix with probability `switch_prob` when
+    both alphas are positive, otherwise by the one whose alpha is positive.
+      Mixup   lam ~ Beta(a, a) rounded to fp32, no box, lam_px = lam, label weight lam
+      CutMix  lam ~ Beta(a, a); r = sqrt(1 - lam), ch = int(H r), cw = int(W r); the centre (cy, cx)
+              is uniform over the frame; y0 = clamp(cy - ch // 2, 0, H), y1 = clamp(cy + ch // 2, 0, H),
+              the same for x; the box (y0, x0, y1 - y0, x1 - x0) holds the partner's pixels on every
+              frame, lam_px = 1, label weight 1 - (y1 - y0) (x1 - x0) / (H W): the area actually kept
+      none    lam_px = 1, no box, label weight 1
+    Both clips of a pair share the box, lam_px and the weight: clip b's target is weight * label[b]
+    + (1 - weight) * label[B-1-b].  The middle clip of an odd batch keeps weight 1.
+
+    Order of the draws: every call makes TWO draws from the generator, whatever B > 1 pairs accept:
+    u = torch.rand(P, 4, float64), row p = (mix?, CutMix?, cy, cx) of pair p, then one int64 that
+    seeds a generator used for this call only, from which the gamma variates g [P, 2, 2] come
+    (lam = g0 / (g0 + g1); g[p, 0] is the Mixup pair, g[p, 1] the CutMix pair, both always drawn).
+    Gamma sampling rejects internally, so it gets a generator of its own: the main stream advances
+    by the same amount per pair in every call and depends on neither the data nor the alphas.
+
+    `last` keeps the last call's host-side draws: {"kind": ["none" | "mixup" | "cutmix"] per pair,
+    "lam": the fp32 lam per pair (1.0 for none), "box": (y0, x0, h, w) per pair, "weight": the
+    fp32 label weight per pair}."""
+
+    def __init__(self, mixup_alpha=0.8, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5, seed=0):
+        self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+        self.prob, self.switch_prob = float(prob), float(switch_prob)
+        if self.mixup_alpha < 0.0 or self.cutmix_alpha < 0.0 or self.mixup_alpha + self.cutmix_alpha == 0.0:
+            raise ValueError(f"ClipMixer needs alphas >= 0, not both zero, got {mixup_alpha}, {cutmix_alpha}")
+        if not 0.0 <= self.prob <= 1.0 or not 0.0 <= self.switch_prob <= 1.0:
+            raise ValueError(f"ClipMixer needs prob and switch_prob within [0, 1], got {prob}, {switch_prob}")
+        self.gen = torch.Generator().manual_seed(int(seed))
+        self.last = {"kind": [], "lam": [], "box": [], "weight": []}
+
+    def draw(self, B, H, W):
+        """The host half: -> (lam_px fp32 [P], box int32 [P,4], weight fp32 [B]) and `last`."""
+        P = B // 2
+        u = torch.rand(P, 4, dtype=torch.float64, generator=self.gen).tolist()
+        sub = torch.Generator().manual_seed(int(torch.randint(0, 2 ** 62, (1,), generator=self.gen)))
+        # an unused alpha (0) still draws, with shape 1, to keep the count fixed
+        alphas = torch.tensor([self.mixup_alpha or 1.0, self.cutmix_alpha or 1.0], dtype=torch.float64)
+        g = torch._standard_gamma(alphas.view(1, 2, 1).expand(P, 2, 2).contiguous(), generator=sub)
+        lam_all = torch.where(g.sum(-1) > 0, g[..., 0] / g.sum(-1), torch.full((), 0.5, dtype=torch.float64))
+        lam_all = lam_all.float()                                   # [P, 2] fp32: what the kernel gets
+        kind, box = [], []
+        lam_px, weight = torch.ones(P, dtype=torch.float32), torch.ones(B, dtype=torch.float32)
+        for p, (u_mix, u_cut, u_cy, u_cx) in enumerate(u):
+            k, bx = "none", (0, 0, 0, 0)
+            if u_mix < self.prob:
+                both = self.mixup_alpha > 0.0 and self.cutmix_alpha > 0.0
+                k = "cutmix" if (u_cut < self.switch_prob if both else self.cutmix_alpha > 0.0) else "mixup"
+            if k == "mixup":
+                lam_px[p] = lam_all[p, 0]
+                weight[p] = weight[B - 1 - p] = lam_all[p, 0]
+            elif k == "cutmix":
+                r = math.sqrt(1.0 - float(lam_all[p, 1]))
+                ch, cw = int(H * r), int(W * r)
+                cy, cx = min(int(u_cy * H), H - 1), min(int(u_cx * W), W - 1)
+                y0, y1 = min(max(cy - ch // 2, 0), H), min(max(cy + ch // 2, 0), H)
+                x0, x1 = min(max(cx - cw // 2, 0), W), min(max(cx + cw // 2, 0), W)
+                bx = (y0, x0, y1 - y0, x1 - x0)
+                weight[p] = weight[B - 1 - p] = 1.0 - (y1 - y0) * (x1 - x0) / (H * W)
+            kind.append(k)
+            box.append(bx)
+        self.last = {"kind": kind, "lam": [float(lam_px[p]) if kind[p] == "mixup" else
+                                           float(lam_all[p, 1]) if kind[p] == "cutmix" else 1.0 for p in range(P)],
+                     "box": box, "weight": weight[:P].tolist()}
+        return lam_px, torch.tensor(box, dtype=torch.int32).view(P, 4), weight
+
+    def __call__(self, clip, label):
+        """clip fp32 [B,3,T,H,W] and label int64 [B] on the device -> (mixed clip, labels_a = label,
+        labels_b = label.flip(0), lam fp32 [B]: the weight of labels_a in each clip's target)."""
+        from .kernels import mix_boxes_check
+        B, H, W = clip.shape[0], clip.shape[-2], clip.shape[-1]
+        P = B // 2
+        lam_px, box, weight = self.draw(B, H, W)
+        mix_boxes_check(box.tolist(), H, W)             # the table lives on the device: checked before it goes up
+        table = torch.cat([box.view(-1), lam_px.view(torch.int32), weight.view(torch.int32)]).to(clip.device)
+        mixed = K.clip_mix(clip.float().contiguous(), table[4 * P:5 * P].view(torch.float32), table[:4 * P].view(P, 4))
+        return mixed, label, label.flip(0), table[5 * P:].view(torch.float32)
+
+
 def resolve_cut_ties(noise, num_mask):
     """noise [B, L] fp32 (CPU): rows where equal values straddle the num_mask cut are
     replaced in place by distinct values ranked as the reference's

@@ -1443,6 +1443,18 @@ def frames_crop_resize_normalize(packed, desc, T, out_hw, mean, std, bgr_swap=Tr
                                                           bool(bgr_swap))
 
 
+@_op("clip_mix", "(Tensor x, Tensor lam_px, Tensor box) -> Tensor")
+def _clip_mix(x, lam_px, box):
+    return _K.clip_mix(x, lam_px, box)
+
+
+_clip_mix.register_fake(lambda x, lam_px, box: torch.empty_like(x))
+
+
+def clip_mix(x, lam_px, box):
+    return torch.ops.ssl_mae.clip_mix(x, lam_px, box)
+
+
 @_op("frames_box_blur", "(Tensor packed, Tensor desc, Tensor boxes, Tensor box_start, float[] weights, int max_h, "
                         "int max_w) -> Tensor")
 def _frames_box_blur(packed, desc, boxes, box_start, weights, max_h, max_w):
@@ -1567,6 +1579,20 @@ _logits_metrics.register_fake(lambda logits, labels, k, segments, dlogits, grad_
 
 def logits_metrics(logits, labels, k, segments=1, dlogits=None, grad_scale=1.0):
     return torch.ops.ssl_mae.logits_metrics(logits, labels, int(k), int(segments), dlogits, float(grad_scale))
+
+
+@_op("soft_ce", "(Tensor logits, Tensor labels_a, Tensor? labels_b, Tensor? lam, float eps, Tensor(a!)? dlogits, "
+                "float grad_scale) -> Tensor", ("dlogits",))
+def _soft_ce(logits, labels_a, labels_b, lam, eps, dlogits, grad_scale):
+    return _K.soft_ce(logits, labels_a, labels_b, lam, eps, dlogits, grad_scale)
+
+
+_soft_ce.register_fake(lambda logits, labels_a, labels_b, lam, eps, dlogits, grad_scale: logits.new_empty(
+    (2,), dtype=torch.float64))
+
+
+def soft_ce(logits, labels_a, labels_b=None, lam=None, eps=0.0, dlogits=None, grad_scale=1.0):
+    return torch.ops.ssl_mae.soft_ce(logits, labels_a, labels_b, lam, float(eps), dlogits, float(grad_scale))
 
 
 @_op("relu_fwd", "(Tensor pre) -> Tensor")

@@ -24,6 +24,13 @@ random-resized crop and a horizontal flip, the same for all its frames and fresh
 (mae_loader.RandomResizedCropFlip, seeded from runtime.seed): the window goes into the
 descriptor of the one resize launch (sm_frames_crop_resize_normalize), so it costs no pixel work
 on the host.  The validation loader is never augmented.
+
+`mix.enabled` (off by default) mixes every training batch with its own flip, clip b with clip
+B-1-b: Mixup or CutMix per pair, the CutMix box the same on every frame of the clip
+(mae_loader.ClipMixer, seeded from runtime.seed; one small upload and one sm_clip_mix launch per
+step, on synthetic clips too).  `training.label_smoothing` smooths the target.  With either, the
+loss is the soft cross-entropy of sm_soft_ce (finetune.SoftCEFn) and `train_loss` in the CSV is
+that soft loss, not the hard-label cross-entropy.  Validation is never mixed or smoothed.
 """
 import argparse
 import functools
@@ -48,11 +55,13 @@ DEFAULTS = {
                 "stride": 4, "image_size": 112},
     "training": {"epochs": 30, "batch_size": 64, "learning_rate": 1e-4, "weight_decay": 0.01, "log_interval": 20,
                  "amp": True, "stage1_epochs": 0, "head_lr": 1e-3, "backbone_lr": 1e-4, "layer_decay": 1.0,
-                 "no_decay_1d": False, "schedule": "constant", "warmup_epochs": 0, "min_lr": 0.0},
+                 "no_decay_1d": False, "schedule": "constant", "warmup_epochs": 0, "min_lr": 0.0,
+                 "label_smoothing": 0.0},
     "model": {"embed_dim": 576, "pretrained_ssl": None, "freeze_backbone": False},
     "optimizer": {"type": "adamw"},
     "evaluation": {"topk": [1, 5]},
     "augment": {"enabled": False, "scale": [0.35, 1.0], "ratio": [0.75, 1.3333], "flip": 0.5},
+    "mix": {"enabled": False, "mixup_alpha": 0.8, "cutmix_alpha": 1.0, "prob": 1.0, "switch_prob": 0.5},
     "synthetic": {"num_train": 96, "num_val": 32},
     "runtime": {"seed": 42, "num_workers": 4},
     "paths": {"save_dir": "results/finetune", "log_dir": "results/logs"},
@@ -63,8 +72,9 @@ def resolve_config(cfg, mode=None, pretrained_ssl=None, epochs=None, batch_size=
                    optimizer=None):
     """The file's values over DEFAULTS, the command line over both; unknown sections or keys
     raise, and so do an unknown mode, two_stage without stage1_epochs, an SSL mode whose
-    checkpoint is missing (train_finetune.py:198-210, :284-286, :306-307) and an `augment` section
-    out of range or enabled without a training split."""
+    checkpoint is missing (train_finetune.py:198-210, :284-286, :306-307), an `augment` section
+    out of range or enabled without a training split, and `training.label_smoothing` or a `mix`
+    value out of range."""
     out = driver.merge_config(DEFAULTS, cfg)
     tr = out["training"]
     out["experiment"]["mode"] = resolve_mode(out, mode)
@@ -114,7 +124,28 @@ def resolve_config(cfg, mode=None, pretrained_ssl=None, epochs=None, batch_size=
     if aug["enabled"] and not out["dataset"]["train_split"]:
         raise ValueError("[ERROR] augment.enabled needs dataset.train_split: the synthetic clips are drawn on the "
                          "device at image_size and have no source frames to crop")
+    if not 0.0 <= float(tr["label_smoothing"]) < 1.0:
+        raise ValueError(f"[ERROR] training.label_smoothing={tr['label_smoothing']}: must lie in [0, 1)")
+    mix = out["mix"]
+    for key in ("mixup_alpha", "cutmix_alpha"):
+        if not float(mix[key]) >= 0.0:
+            raise ValueError(f"[ERROR] mix.{key}={mix[key]}: must be >= 0")
+    if mix["enabled"] and float(mix["mixup_alpha"]) == 0.0 and float(mix["cutmix_alpha"]) == 0.0:
+        raise ValueError("[ERROR] mix.enabled needs mixup_alpha > 0 or cutmix_alpha > 0")
+    for key in ("prob", "switch_prob"):
+        if not 0.0 <= float(mix[key]) <= 1.0:
+            raise ValueError(f"[ERROR] mix.{key}={mix[key]}: must lie in [0, 1]")
     return out
+
+
+def build_mixer(cfg):
+    """The training batches' mae_loader.ClipMixer, seeded from runtime.seed; None when `mix` is off."""
+    mix = cfg["mix"]
+    if not mix["enabled"]:
+        return None
+    from .mae_loader import ClipMixer
+    return ClipMixer(mix["mixup_alpha"], mix["cutmix_alpha"], mix["prob"], mix["switch_prob"],
+                     seed=int(cfg["runtime"]["seed"]))
 
 
 def freeze_rule(cfg):
@@ -146,9 +177,10 @@ def set_lr_mult(optimizer, base_lrs, mult):
             g["lr"] = base * float(mult)
 
 
-def train_one_epoch(model, loader, optimizer, scaler, device, cfg, log, step_hook=None):
+def train_one_epoch(model, loader, optimizer, scaler, device, cfg, log, step_hook=None, mixer=None, mix_hook=None):
     """train_finetune.py:84-124 as driver.train_pass, the loss sum kept on the device; returns the
-    average loss over the steps."""
+    average loss over the steps (the soft loss with `mixer` or training.label_smoothing).
+    `mix_hook(step, info)` gets every step's {"labels_b", "lam", "draws"}."""
     model.train()
     tr = cfg["training"]
     t0 = time.time()
@@ -161,7 +193,12 @@ def train_one_epoch(model, loader, optimizer, scaler, device, cfg, log, step_hoo
             log(f"[INFO] step={step + 1}/{n} loss={loss.item():.4f}")
 
     sums = torch.zeros(2, dtype=torch.float64, device=device)     # (loss, loss * batch)
-    steps, _ = driver.train_pass(model, loader, optimizer, device, tr["amp"], sums, scaler, on_step)
+    def on_mix(step, labels_b, lam):
+        mix_hook(step, {"labels_b": labels_b, "lam": lam, "draws": mixer.last})
+
+    steps, _ = driver.train_pass(model, loader, optimizer, device, tr["amp"], sums, scaler, on_step, mixer=mixer,
+                                 label_smoothing=float(tr["label_smoothing"]),
+                                 on_mix=on_mix if mixer is not None and mix_hook is not None else None)
     avg_loss = float(sums[0].item()) / max(1, steps)
     log(f"[INFO] Epoch train finished, avg_loss={avg_loss:.4f}, time={time.time() - t0:.1f}s")
     return avg_loss
@@ -207,7 +244,9 @@ def build_loaders(cfg, device):
 
 def main(argv=None, hooks=None):
     """`hooks` (tests, measurement scripts): {"step": f(epoch, step, logits, label), "epoch":
-    f(epoch, model, optimizer)}, called after every optimizer step / at the end of every epoch."""
+    f(epoch, model, optimizer), "mix": f(epoch, step, info)}, called after every optimizer step / at
+    the end of every epoch / after every batch's mix with info = {"labels_b", "lam", "draws"}: the
+    partner labels and the labels' weights on the device, and ClipMixer.last."""
     ap = argparse.ArgumentParser(description="Fine-tune VideoClassifier: ft_random, linear_probe, ft_ssl, two_stage.")
     ap.add_argument("--config", default="configs/finetune.yaml")
     ap.add_argument("--mode", default=None, help="override experiment.mode (ft_random|linear_probe|ft_ssl|two_stage)")
@@ -235,6 +274,8 @@ def main(argv=None, hooks=None):
         print(f"[INFO] Augmentation: clip-consistent random-resized crop scale={list(aug['scale'])} "
               f"ratio={list(aug['ratio'])}, flip p={aug['flip']} (training split only, seed {cfg['runtime']['seed']})")
 
+    mixer = build_mixer(cfg)
+
     def load_for_mode(model, ssl):
         if mode == "ft_random":
             print("[INFO] ft_random: skip SSL loading (random init)")
@@ -258,6 +299,11 @@ def main(argv=None, hooks=None):
     rows, ckpts = [], []
     with open(log_dir / f"finetune_{mode}.log", "a", encoding="utf-8") as log_f:
         log = functools.partial(log_line, log_f)
+        if mixer is not None:
+            mix = cfg["mix"]
+            log(f"[INFO] Mixing: clip-consistent Mixup alpha={mix['mixup_alpha']} / CutMix alpha={mix['cutmix_alpha']} "
+                f"of clip b with clip B-1-b, p={mix['prob']}, CutMix share {mix['switch_prob']}, label smoothing "
+                f"{tr['label_smoothing']} (training batches only, seed {cfg['runtime']['seed']})")
         best_top1 = -1.0      # the first validated epoch always leaves a checkpoint
         for epoch in range(1, epochs + 1):
             if two_stage and epoch == stage1 + 1:
@@ -269,9 +315,10 @@ def main(argv=None, hooks=None):
             mult = epoch_lr_mult(epoch - 1, cfg)
             set_lr_mult(optimizer, base_lrs, mult)
             t0 = time.time()
-            step_hook = hooks.get("step")
+            step_hook, mix_hook = hooks.get("step"), hooks.get("mix")
             avg_loss = train_one_epoch(model, train_loader, optimizer, scaler, device, cfg, log,
-                                       (lambda s, lg, y, _e=epoch: step_hook(_e, s, lg, y)) if step_hook else None)
+                                       (lambda s, lg, y, _e=epoch: step_hook(_e, s, lg, y)) if step_hook else None,
+                                       mixer, (lambda s, info, _e=epoch: mix_hook(_e, s, info)) if mix_hook else None)
             acc = evaluate(model, val_loader, device, topk, log, split="val")
             rows.append({"epoch": epoch, "train_loss": round(avg_loss, 6), "val_top1": round(acc[1], 6),
                          "val_topk": round(acc[k_max], 6), "lr": round(max(base_lrs) * mult, 6) if base_lrs else 0.0,
